@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Forward-throughput benchmark of the tfimm hot path on MI355X (contract: see task brief).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet50|vit_base_patch16_224|...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet50|vit_base_patch16_224|...] [--full]
+                  [--dump-outputs DIR]
+
+A plain run does only what its headline figure needs: set-up (including the choice of launch mode under --branches auto),
+W warm-up steps, the K timed steps and the result line.  ``--full`` adds everything listed under "Printed JSON" below that
+is not that figure: per-step medians, the sustained window and telemetry, per-kernel rooflines, the CPU baseline and parity
+statements, the other BASELINE configurations (``also``) and the bit-equality checks of the launch modes and the exchange.
+``--dump-outputs DIR`` writes the logits of the main workload's last timed step (and, N > 1, the gathered logits of all
+ranks) as float32 ``DIR/logits.npy`` / ``DIR/gathered_logits.npy``; weights and inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 
 A "step" is one forward pass of the workload's model over one synthetic, already preprocessed bf16
 batch that is resident in HBM before the timed region starts.  Weak scaling: every rank processes
@@ -104,6 +113,11 @@ def parse():
     ap.add_argument("--backend", default=os.environ.get("TFIMM_BENCH_BACKEND", "nccl"), choices=["nccl", "gloo"],
                     help="torch.distributed backend of the logits exchange: nccl (= RCCL over xGMI, one rank per GPU) or gloo "
                          "(host sockets; lets several ranks share one GPU -- how the N > 1 path is exercised on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (medians, telemetry, rooflines, CPU "
+                         "baseline, parity, the other BASELINE configurations)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the main workload's logits of the last timed step to DIR/logits.npy (float32)")
     return ap.parse_args()
 
 
@@ -165,8 +179,10 @@ def synthetic_batch(cfg, batch, seed):
 _CAPI = {}     # the C-ABI communicator of this process (one per run: RCCL communicators are not cheap)
 
 
-def measure(model, batch, micro_batch, steps, warmup, world, kernel_events, dist, graph=True, branches="auto"):
-    """Timed region: barrier + sync, K steps, sync + barrier.  Returns seconds, per-kind kernel time, handles."""
+def measure(model, batch, micro_batch, steps, warmup, world, kernel_events, dist, graph=True, branches="auto", full=True):
+    """Timed region: barrier + sync, K steps, sync + barrier.  Returns seconds, per-kind kernel time, handles.
+    ``full=False`` (a plain bench run): set-up, warm-up and the timed region only -- no telemetry, no bit-equality checks,
+    no median / other-mode / sustained passes (their fields are None)."""
     import torch
     cfg = model.cfg
     x = synthetic_batch(cfg, batch, 2021 + (dist.get_rank() if dist is not None else 0))
@@ -193,7 +209,7 @@ def measure(model, batch, micro_batch, steps, warmup, world, kernel_events, dist
         comm = _CAPI.get("comm") or _CAPI.setdefault("comm", CapiComm(dist))
     pipe = PipelinedGather(batch, out_t.C, torch.float32, "cuda", dist, comm=comm) if (dist is not None and not sync_gather) else None
     gathered = torch.empty(world * batch, out_t.C, dtype=torch.float32, device="cuda") if (dist is not None and sync_gather) else None
-    tele = Telemetry(torch.cuda.current_device())
+    tele = Telemetry(torch.cuda.current_device()) if full else None
 
     host_gather = dist is not None and dist.get_backend() == "gloo"
     use_graph = graph and mb == batch
@@ -256,7 +272,7 @@ def measure(model, batch, micro_batch, steps, warmup, world, kernel_events, dist
                     forked = None
     # the recording that will be timed must give the bits of the single-branch recording (checked once, before the warm-up)
     forked_bit_equal = None
-    if forked is not None:
+    if forked is not None and full:
         captured.replay()
         one = logits.clone()
         assert torch.equal(one, plans[batch].tensor_view(out_t).view(batch, out_t.C).float()), "recorded sink differs from the plan's output"
@@ -291,7 +307,8 @@ def measure(model, batch, micro_batch, steps, warmup, world, kernel_events, dist
 
     for _ in range(warmup):
         step()
-    tele.start()              # (sampler process: shader clock / socket power) -- started in front of the barrier, so that its
+    if tele is not None:
+        tele.start()          # (sampler process: shader clock / socket power) -- started in front of the barrier, so that its
     torch.cuda.synchronize()  # round trip is not idle GPU time between the warm-up and the first timed step
     if dist is not None:
         dist.barrier()
@@ -306,29 +323,35 @@ def measure(model, batch, micro_batch, steps, warmup, world, kernel_events, dist
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    telemetry = tele.stop().summary()
+    telemetry = tele.stop().summary() if tele is not None else {}
     if pipe is not None:
         gathered = pipe.last()
+    # what a caller of the timed path receives from its last step (the passes below write the same buffers again)
+    last_logits = logits.clone()
+    last_gathered = None if gathered is None else gathered.clone()
+    torch.cuda.synchronize()
     # per-step durations for the median: the same K steps once more with an event on the launch stream between them -- a pass
     # of its own (an event record between two graph launches costs a step of ResNet-50 about 50 us: it stays out of `value`)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
-    marks[0].record()
-    for i in range(steps):
-        step()
-        marks[i + 1].record()
-    if pipe is not None:
-        pipe.drain()
-    torch.cuda.synchronize()
-    per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
-    median_ms = per_step[steps // 2] if steps % 2 else 0.5 * (per_step[steps // 2 - 1] + per_step[steps // 2])
+    median_ms = None
+    if full:
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+        marks[0].record()
+        for i in range(steps):
+            step()
+            marks[i + 1].record()
+        if pipe is not None:
+            pipe.drain()
+        torch.cuda.synchronize()
+        per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
+        median_ms = per_step[steps // 2] if steps % 2 else 0.5 * (per_step[steps // 2 - 1] + per_step[steps // 2])
     # the exchange step really delivered this rank's logits (and, world = 1, nothing else): bit for bit
     gather_bit_equal = None
-    if dist is not None:
+    if dist is not None and full:
         rk = dist.get_rank()
         gather_bit_equal = bool(torch.equal(gathered[rk * batch:(rk + 1) * batch], logits))
     # the other launch mode under the SAME protocol (warm-up, K steps between synchronisations), so that kernel changes stay
     # visible round over round whichever mode wins on a box
-    if forked is not None and captured is not None:
+    if forked is not None and captured is not None and full:
         for _ in range(warmup):
             captured.replay()
         torch.cuda.synchronize()
@@ -341,7 +364,7 @@ def measure(model, batch, micro_batch, steps, warmup, world, kernel_events, dist
     # step is 70 ms -- a handful of telemetry samples -- and a part that has not reached its steady clock / power state yet
     sustained = None
     best = forked if forked is not None else captured
-    if best is not None:
+    if best is not None and full:
         n_s = max(steps, int(0.6 / max(dt / steps, 1e-4)) + 1)
         torch.cuda.synchronize()
         tele.start()
@@ -370,11 +393,11 @@ def measure(model, batch, micro_batch, steps, warmup, world, kernel_events, dist
             s_["n"] += 1
             s_["flops"] += flops
     return dict(seconds=dt, ms_per_step=dt / steps * 1e3, median_ms_per_step=median_ms, gather_bit_equal=gather_bit_equal,
-                forked_bit_equal=forked_bit_equal, kernels=stats, logits=logits, x=x, prog=prog, telemetry=telemetry,
+                forked_bit_equal=forked_bit_equal, kernels=stats, logits=last_logits, x=x, prog=prog, telemetry=telemetry,
                 sustained=sustained, exchange_mode=(None if dist is None else "synchronous on the launch stream" if pipe is None else
                                                     "asynchronous, double-buffered (dp.PipelinedGather): step i's all-gather under step i + 1"
                                                     + (", ncclAllGather through the C ABI (tfimm_hip_dp_all_gather_logits)" if comm is not None else "")),
-                graph=captured is not None, gathered=gathered, branches=(n_br if forked is not None else 1),
+                graph=captured is not None, gathered=last_gathered, branches=(n_br if forked is not None else 1),
                 hybrid_cut=(hybrid_cut if forked is not None and hybrid_cut is not None and getattr(forked, "cut_op", None) == hybrid_cut else None),
                 n_ops=len(prog.ops),
                 single_branch_ms=single_ms, forked_ms=forked_ms,
@@ -717,8 +740,8 @@ def run_workload(name, args, world, rank, dist, steps, warmup, batch=0, micro_ba
     batch = batch or wl["batch"]
     model = build_model(wl["model"])
     torch.cuda.empty_cache()
-    r = measure(model, batch, micro_batch, steps, warmup, world, not args.no_kernel_events, dist, graph=not args.no_graph,
-                branches=args.branches)
+    r = measure(model, batch, micro_batch, steps, warmup, world, args.full and not args.no_kernel_events, dist, graph=not args.no_graph,
+                branches=args.branches, full=args.full)
     ms = r["ms_per_step"]
     per_rank = [ms]
     if dist is not None:
@@ -739,7 +762,7 @@ def run_workload(name, args, world, rank, dist, steps, warmup, batch=0, micro_ba
             # `frac` is the kernels by themselves (one branch, launch by launch)
             rl["frac_timed_mode"] = round(rl["algorithmic_bytes_per_step"] / (ms * 1e-3) / 1e9 / rl["peak"], 4)
         out = dict(value=round(total / ms * 1e3, 1), unit="images/sec", ms_per_step=round(ms, 4),
-                   median_ms_per_step=round(r["median_ms_per_step"], 4), gather_bit_equal=r["gather_bit_equal"],
+                   median_ms_per_step=_r(r["median_ms_per_step"], 4), gather_bit_equal=r["gather_bit_equal"],
                    forked_bit_equal_to_single=r["forked_bit_equal"], per_gpu_batch=batch,
                    global_batch=total, per_rank_ms=per_rank, model=wl["model"], input_size=int(model.cfg.input_size[0]),
                    launch=("eager" if not r["graph"] else "hipGraph replay" if r["branches"] == 1 else
@@ -761,7 +784,7 @@ def run_workload(name, args, world, rank, dist, steps, warmup, batch=0, micro_ba
                    power_w_mean=r["telemetry"].get("energy_power_w") or r["telemetry"].get("power_w_mean"),
                    power_cap_w=r["telemetry"].get("power_cap_w"), telemetry=r["telemetry"], sustained=r["sustained"],
                    exchange_mode=r["exchange_mode"],
-                   roofline=rl)
+                   roofline=rl, outputs=dict(logits=r["logits"], gathered_logits=r["gathered"]))
         out["energy"] = energy_of(name, flops_img, batch, prog.weight_bytes(), r["sustained"])
         if with_cpu:
             cpu, xs, ys, fs = cpu_baseline(model, wl["model"], target_seconds=cpu_seconds, parity_images=parity_images)
@@ -880,6 +903,16 @@ def write_detail(detail):
         print(f"warning: could not write {path}: {e}", file=sys.stderr)
 
 
+def dump_outputs(directory, outputs):
+    """What the timed path handed its caller in the last timed step, as float32 .npy files (logits: batch x classes, 1 MB for
+    ResNet-50 at 256; the gathered logits of all ranks when N > 1)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in outputs.items():
+        if t is not None:
+            np.save(os.path.join(directory, f"{name}.npy"), t.detach().float().cpu().numpy().astype(np.float32))
+
+
 def main():
     args = parse()
     launched = "WORLD_SIZE" in os.environ
@@ -910,12 +943,18 @@ def main():
     if args.gpus != world and rank == 0:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}; reporting n_gpus={world}", file=sys.stderr)
 
+    cpu = args.full and not args.no_cpu_baseline
     main_r = run_workload(args.workload, args, world, rank, dist, args.steps, args.warmup, batch=args.batch,
-                          micro_batch=args.micro_batch, with_cpu=(world == 1 and not args.no_cpu_baseline),
-                          with_parity=(world > 1 and not args.no_cpu_baseline))
+                          micro_batch=args.micro_batch, with_cpu=(world == 1 and cpu), with_parity=(world > 1 and cpu))
+    if rank == 0:
+        outputs = main_r.pop("outputs")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
+        del outputs
     # N > 1: ViT-B/16 (the other half of the headline metric) and EfficientNet-B4 -- BASELINE.json configs[4] is B4 at
-    # 256 per GPU x 8 GPUs = 2048 global, so the driver's plain `bench.py --gpus 8` measures it
-    extra = args.extra if args.extra is not None else (DEFAULT_EXTRA if world == 1 else "vit_base_patch16_224,efficientnet_b4")
+    # 256 per GPU x 8 GPUs = 2048 global, so `bench.py --gpus 8 --full` measures it; a plain run measures the main workload only
+    extra = args.extra if args.extra is not None else (
+        "" if not args.full else DEFAULT_EXTRA if world == 1 else "vit_base_patch16_224,efficientnet_b4")
     also = {}
     for name in [n for n in extra.split(",") if n and n != args.workload]:
         try:
@@ -927,7 +966,9 @@ def main():
             # (every BASELINE configuration carries parity next to its throughput: 128 images each on one GPU)
             also[name] = run_workload(name, args, world, rank, dist, args.steps if vit else max(3, args.steps // 2),
                                       args.warmup if vit else max(2, args.warmup // 2),
-                                      with_cpu=(world == 1 and not args.no_cpu_baseline), cpu_seconds=6.0, parity_images=128)
+                                      with_cpu=(world == 1 and cpu), cpu_seconds=6.0, parity_images=128)
+            if also[name] is not None:
+                also[name].pop("outputs", None)
         except Exception as e:  # noqa: BLE001
             if dist is not None:
                 raise                     # a rank that skips a collective would hang the others

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,7 +59,7 @@ def test_every_baseline_config_is_a_workload():
 def test_one_rank_through_the_launcher():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--steps", "3",
                         "--warmup", "1", "--workload", "vit_tiny_patch16_224", "--batch", "8", "--no-cpu-baseline",
-                        "--extra", ""], capture_output=True, text=True, timeout=900)
+                        "--extra", "", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert len(r.stdout.strip().splitlines()) == 1, r.stdout[:2000]      # the JSON line and nothing else (RCCL's banner goes to stderr)
     line = json.loads(r.stdout)
@@ -79,6 +80,42 @@ def test_one_rank_through_the_launcher():
     if tl["source"] is not None:
         assert 100 < detail["sclk_mhz_mean"] < 3000 and 100 < detail["power_w_mean"] <= 1.05 * detail["power_cap_w"]
         assert detail["sustained"]["steps"] >= 3 and detail["sustained"]["ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_main_workload_only_and_dumps_its_logits(tmp_path):
+    """Without --full: the headline fields, nothing measured beyond them, and the logits of the last timed step on disk."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--workload", "vit_tiny_patch16_224", "--batch", "8", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, env=dict(os.environ, TFIMM_BENCH_DETAIL=str(tmp_path / "d.json")))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert len(r.stdout.strip().splitlines()) == 1, r.stdout[:2000]
+    line = json.loads(r.stdout)
+    assert line["metric"] == "images/sec (fwd, bf16)" and line["unit"] == "images/sec" and line["dtype"] == "bf16"
+    assert line["higher_is_better"] is True and line["steps"] == 3 and line["value"] > 0
+    assert abs(line["value"] - 8 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["also"] == {}
+    logits = np.load(tmp_path / "logits.npy")
+    assert logits.dtype == np.float32 and logits.shape == (8, 1000) and np.isfinite(logits).all()
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    import bench
+    import torch
+    bench.dump_outputs(str(tmp_path / "out"), dict(logits=torch.arange(6, dtype=torch.bfloat16).view(2, 3), gathered_logits=None))
+    got = np.load(tmp_path / "out" / "logits.npy")
+    assert got.dtype == np.float32 and got.tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert sorted(os.listdir(tmp_path / "out")) == ["logits.npy"]
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
 
 
 def bench_limit():

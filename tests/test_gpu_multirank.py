@@ -100,7 +100,7 @@ def test_bench_one_rank_through_rccl(exchange):
     driver's contract.  The gathered logits must be the local ones bit for bit."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--backend", "nccl", "--steps", "3",
                         "--warmup", "1", "--workload", "vit_tiny_patch16_224", "--batch", "8", "--no-cpu-baseline",
-                        "--extra", ""], capture_output=True, text=True, timeout=900,
+                        "--extra", "", "--full"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, TFIMM_DP_EXCHANGE=exchange, TFIMM_BENCH_DETAIL=os.path.join(ROOT, f"bench_detail_{exchange}.json")))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -9,7 +9,7 @@ for w in $WL; do
   i=0
   for set in "TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE"; do
     i=$((i+1)); rm -rf $O/l2a_${w}_$i
-    timeout 600 rocprofv3 --pmc $set --output-format csv -d $O/l2a_${w}_$i -o p -- python $R/bench.py --workload $w --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-kernel-events --branches 1 --extra "" > $O/l2a_${w}_$i.log 2>&1
+    timeout 600 rocprofv3 --pmc $set --output-format csv -d $O/l2a_${w}_$i -o p -- python $R/bench.py --full --workload $w --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-kernel-events --branches 1 --extra "" > $O/l2a_${w}_$i.log 2>&1
     echo "$w pass $i rc=$?"
   done
   python - "$O" "$w" <<'PY' > $O/l2_audit_$w.txt

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; export TMPDIR=/tmp; 
 W=${1:-vit_base_patch16_224}
 rm -rf $O/mfma_$W
 timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace --output-format csv -d $O/mfma_$W -o m -- \
-  python $R/bench.py --workload $W --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-kernel-events --extra "" > $O/mfma_$W.log 2>&1
+  python $R/bench.py --full --workload $W --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-kernel-events --extra "" > $O/mfma_$W.log 2>&1
 python - $O/mfma_$W $W > $O/mfma_busy_$W.txt <<'PY'
 import csv, sys, glob, collections
 d, w = sys.argv[1], sys.argv[2]

@@ -10,7 +10,7 @@ W=${1:-efficientnet_b4}
 rm -rf $O/pipe_$W
 timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_WAVES \
   --kernel-trace --output-format csv -d $O/pipe_$W -o m -- \
-  python $R/bench.py --workload $W --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-kernel-events --extra "" > $O/pipe_$W.log 2>&1
+  python $R/bench.py --full --workload $W --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-kernel-events --extra "" > $O/pipe_$W.log 2>&1
 echo "rocprof rc=$?"; tail -3 $O/pipe_$W.log | cut -c1-300
 python - $O/pipe_$W $W > $O/pipe_busy_$W.txt <<'PY'
 import csv, sys, glob, collections

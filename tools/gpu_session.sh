@@ -48,7 +48,7 @@ for d in glob.glob("/sys/class/drm/card*/device/hwmon/hwmon*"):
 PY
       grep -v amdgpu.ids $O/recon.txt | cut -c1-3000 ;;
     bench)
-      TFIMM_BENCH_DETAIL=$O/bench_detail.json timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$? line $(wc -c < $O/bench.json) bytes"; grep -v "^bench detail" $O/bench.err | tail -3 | cut -c1-400
+      TFIMM_BENCH_DETAIL=$O/bench_detail.json timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$? line $(wc -c < $O/bench.json) bytes"; grep -v "^bench detail" $O/bench.err | tail -3 | cut -c1-400
       python - <<PY
 import json
 d = json.loads(open("$O/bench_detail.json").read())
@@ -65,10 +65,10 @@ PY
       ;;
     rccl)
       for mode in async sync capi; do
-        TFIMM_BENCH_DETAIL=$O/bench_rccl_world1_$mode.json TFIMM_BENCH_SYNC_GATHER=$([ $mode = sync ] && echo 1 || echo 0) TFIMM_DP_EXCHANGE=$([ $mode = capi ] && echo capi || echo torch) timeout 900 python bench.py --gpus 1 --spawn --backend nccl --steps 20 --warmup 5 --no-cpu-baseline --extra "" > /dev/null 2> $O/bench_rccl_world1_$mode.err
+        TFIMM_BENCH_DETAIL=$O/bench_rccl_world1_$mode.json TFIMM_BENCH_SYNC_GATHER=$([ $mode = sync ] && echo 1 || echo 0) TFIMM_DP_EXCHANGE=$([ $mode = capi ] && echo capi || echo torch) timeout 900 python bench.py --full --gpus 1 --spawn --backend nccl --steps 20 --warmup 5 --no-cpu-baseline --extra "" > /dev/null 2> $O/bench_rccl_world1_$mode.err
         echo "rccl $mode rc=$?"
       done
-      TFIMM_BENCH_DETAIL=$O/bench_no_exchange.json timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --extra "" > /dev/null 2> $O/bench_no_exchange.err
+      TFIMM_BENCH_DETAIL=$O/bench_no_exchange.json timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --extra "" > /dev/null 2> $O/bench_no_exchange.err
       python - <<PY
 import json
 for m in ("rccl_world1_async", "rccl_world1_sync", "rccl_world1_capi", "no_exchange"):
@@ -91,7 +91,7 @@ PY
       cd /tmp
       for m in $WLS; do
         rm -rf $O/prof_$m
-        timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$m -o $m -- python $R/bench.py --workload $m --steps 5 --warmup 2 --no-graph --no-cpu-baseline --no-kernel-events --extra "" > $O/prof_$m.log 2>&1; echo "rocprof $m rc=$?"
+        timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$m -o $m -- python $R/bench.py --full --workload $m --steps 5 --warmup 2 --no-graph --no-cpu-baseline --no-kernel-events --extra "" > $O/prof_$m.log 2>&1; echo "rocprof $m rc=$?"
         f=$(find $O/prof_$m -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${m}_kernel_stats.csv && head -4 $O/${m}_kernel_stats.csv | cut -c1-170
         rm -rf $O/prof_$m
       done
@@ -119,7 +119,7 @@ PY
           n=${spec%%=*}; lib=${spec#*=}
           for wl in ${AB_WL:-efficientnet_b4}; do
             if [ "$lib" = "-" ]; then unset TFIMM_HIP_LIB; else export TFIMM_HIP_LIB=$R/$lib; fi
-            TFIMM_BENCH_DETAIL=$O/ab_${n}_${wl}_$rep.json timeout 600 python bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --extra "" ${AB_ARGS:-} > /dev/null 2> $O/ab_${n}_${wl}_$rep.err
+            TFIMM_BENCH_DETAIL=$O/ab_${n}_${wl}_$rep.json timeout 600 python bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --extra "" ${AB_ARGS:-} > /dev/null 2> $O/ab_${n}_${wl}_$rep.err
             python - <<PY
 import json
 try:

@@ -12,7 +12,7 @@ WL=${@:-resnet50 vit_base_patch16_224 swin_base_patch4_window7_224 efficientnet_
 for w in $WL; do
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/traffic_${w}_$c
-    timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/traffic_${w}_$c -o t -- python $R/bench.py --workload $w --steps $STEPS --warmup $WARM --no-graph --no-cpu-baseline --no-kernel-events --extra "" > $O/traffic_${w}_$c.log 2>&1
+    timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/traffic_${w}_$c -o t -- python $R/bench.py --full --workload $w --steps $STEPS --warmup $WARM --no-graph --no-cpu-baseline --no-kernel-events --extra "" > $O/traffic_${w}_$c.log 2>&1
     echo "$w $c rc=$?"
   done
 done
