@@ -460,11 +460,12 @@ TFIMM_API int tfimm_hip_attention_probs(const void* qkv, void* probs, int B, int
 
 /* ---------------------------------------------------------------------------------------
  * tfimm_hip_group_norm: GroupNormalization over NHWC (layers/norm.py:37-165, group_normalize): per (image, group)
- * mean / population variance over (H, W, C/groups), y = x*inv + (beta - mean*inv), inv = rsqrt(var+eps)*gamma
+ * mean / population variance over (H, W, C/groups), y = (x - mean)*inv + beta, inv = rsqrt(var+eps)*gamma
  * (tf.nn.batch_normalization), then act, then (+ residual, act_after_res) when residual != NULL -- the
  * norm + activation + shortcut add of a ResNet block whose norm_layer is "group_norm" (resnet.py:269-290).
  * x / residual / y: bf16 [B][rows][C]; gamma / beta: fp32 [C]; stats_ws: int64 [B][groups][2] scratch (zeroed here): sum and
- * sum of squares in 2^-20 fixed point, so the statistics do not depend on the order the workgroups add them in.
+ * sum of squares of x minus the group's first value, in 2^-28 fixed point, so the statistics do not depend on the order the
+ * workgroups add them in.
  * ------------------------------------------------------------------------------------- */
 TFIMM_API int tfimm_hip_group_norm(const void* x, const float* gamma, const float* beta, const void* residual, void* y,
                          void* stats_ws, int B, int rows, int C, int groups, float eps, int act,

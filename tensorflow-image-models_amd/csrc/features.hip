@@ -73,9 +73,18 @@ extern "C" int tfimm_hip_attention_probs(const void* qkv, void* probs, int B, in
 // =====================================================================================================================
 // group normalisation
 // =====================================================================================================================
-// Pass 1: per (image, group) sum and sum of squares.  A workgroup takes a run of rows of ONE image; a thread keeps one
+// Pass 1: per (image, group) sum and sum of squares of d = x - pilot, the pilot being the group's first value in the image's
+// first row (any value of the group would do: it only has to be near the mean, so that sum d^2 - (sum d)^2 / n does not cancel
+// when the mean is many standard deviations from zero).  A workgroup takes a run of rows of ONE image; a thread keeps one
 // channel vector (V = 8 or 1 channels) in registers across its rows, the per-channel totals meet in LDS, the G group
 // totals leave with one global atomic pair per group and workgroup.
+// Fixed point at 2^-28 (not the 2^-20 of the squeeze sums): a group of standard deviation 1e-3 has d^2 ~ 1e-6 per value, which
+// 2^-20 would hold to a few bits.  Range: a (image, group) total of d^2 up to 3.4e10.
+#define TFIMM_GN_SCALE 268435456.0f
+#define TFIMM_GN_INV_SCALE (1.0 / 268435456.0)
+__device__ __forceinline__ tfimm_sq_t gn_from_float(float v) { return __float2ll_rn(v * TFIMM_GN_SCALE); }
+__device__ __forceinline__ float gn_pilot(const bf16_t* xb, int c, int S) { return bf2f(xb[(c / S) * S]); }
+
 template <int V>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict__ x, tfimm_sq_t* __restrict__ stats, int rows,
                                                        int C, int G, int rows_per_block) {
@@ -94,9 +103,12 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
   const bf16_t* xb = x + (int64_t)b * rows * C;
   if (r_in < rstep) {
     for (int v = v_in; v < nvec; v += nvp) {
-      float s[V], q[V];
+      float s[V], q[V], pl[V];
 #pragma unroll
-      for (int e = 0; e < V; ++e) s[e] = q[e] = 0.f;
+      for (int e = 0; e < V; ++e) {
+        s[e] = q[e] = 0.f;
+        pl[e] = gn_pilot(xb, v * V + e, C / G);
+      }
       for (int r = r0 + r_in; r < r1; r += rstep) {
         float f[V];
         if constexpr (V == 8) {
@@ -106,14 +118,15 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
         }
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-          s[e] += f[e];
-          q[e] = fmaf(f[e], f[e], q[e]);
+          const float d = f[e] - pl[e];
+          s[e] += d;
+          q[e] = fmaf(d, d, q[e]);
         }
       }
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        sq_add(&gn_lds[2 * (v * V + e)], sq_from_float(s[e]));
-        sq_add(&gn_lds[2 * (v * V + e) + 1], sq_from_float(q[e]));
+        sq_add(&gn_lds[2 * (v * V + e)], gn_from_float(s[e]));
+        sq_add(&gn_lds[2 * (v * V + e) + 1], gn_from_float(q[e]));
       }
     }
   }
@@ -140,12 +153,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict_
   extern __shared__ __attribute__((aligned(16))) float gn_ms[];       // [G][2]: mean, rstd
   const int b = blockIdx.y;
   const int S = C / G;
-  const float inv_n = 1.f / ((float)rows * (float)S);
+  const double inv_n = 1.0 / ((double)rows * (double)S);
   for (int g = threadIdx.x; g < G; g += 256) {
-    const double s = (double)stats[((int64_t)b * G + g) * 2] * (1.0 / 1048576.0);
-    const double q = (double)stats[((int64_t)b * G + g) * 2 + 1] * (1.0 / 1048576.0);
-    const float mean = (float)(s * inv_n);
-    const float var = fmaxf((float)(q * inv_n - (s * inv_n) * (s * inv_n)), 0.f);
+    const double s = (double)stats[((int64_t)b * G + g) * 2] * TFIMM_GN_INV_SCALE * inv_n;       // mean of d
+    const double q = (double)stats[((int64_t)b * G + g) * 2 + 1] * TFIMM_GN_INV_SCALE * inv_n;   // mean of d^2
+    const float mean = (float)((double)gn_pilot(x + (int64_t)b * rows * C, g * S, S) + s);
+    const float var = fmaxf((float)(q - s * s), 0.f);
     gn_ms[2 * g] = mean;
     gn_ms[2 * g + 1] = rsqrtf(var + eps);
   }
@@ -171,7 +184,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict_
       const int c = v * V + e;
       const int g = c / S;
       const float inv = gn_ms[2 * g + 1] * gamma[c];                   // tf.nn.batch_normalization (layers/norm.py:104)
-      float o = f[e] * inv + (beta[c] - gn_ms[2 * g] * inv);
+      // (x - mean) * inv + beta: x * inv and mean * inv would cancel to the output where the mean and inv are both large
+      float o = fmaf(f[e] - gn_ms[2 * g], inv, beta[c]);
       o = apply_act(o, act);
       if (residual) o = apply_act(o + rs[e], act_after);
       f[e] = o;

@@ -120,3 +120,22 @@ def test_recorded_zeroing_writes_its_value_on_every_replay(nbytes, offset):
             assert int((buf != value).sum().item()) == 0, f"replay {r}: {nbytes} bytes at +{offset}, value {value:#x}"
             assert int((base[:offset] != 0x55).sum().item()) == 0 and int((base[offset + nbytes:] != 0x55).sum().item()) == 0, \
                 f"replay {r}: bytes outside the range were written"
+
+
+def test_swin_one_window_per_workgroup_kernel_holds_the_tight_bars():
+    """attn_window_kernel, the one-window-per-workgroup Swin kernel that TFIMM_ATTN_WIN_V1=1 selects instead of the chunked
+    attn_window_persist_kernel (read once per process, hence the subprocess): the tight_swin_tiles_* cases of head dim 32 and
+    7 x 7 windows, same references, same bars."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = sorted(n for n in hip_checks.CASES if n.startswith("tight_swin_tiles_w7"))
+    assert len(names) >= 8
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]; import hip_checks\n"
+            "for n in %r:\n"
+            "    e, t = hip_checks.run_case(n); print(n, e, t); assert e <= t, (n, e, t)\n"
+            % (root, os.path.join(root, "tensorflow-image-models_amd"), os.path.join(root, "tests"), names))
+    env = dict(os.environ, TFIMM_ATTN_WIN_V1="1")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
