@@ -537,6 +537,51 @@ typedef struct tfimm_mlp_desc {
 TFIMM_API int tfimm_hip_mlp_fused(const tfimm_mlp_desc* d, void* stream);
 
 /* =======================================================================================
+ * MXFP8 PATH (csrc/mx.hip; selected by TFIMM_PRECISION=fp8, tfimm/engine/precision.py)
+ *
+ * OCP microscaling FP8: e4m3fn elements (OCP encoding, not fnuz) in blocks of 32 along K, one E8M0 scale byte per block
+ * (2^(byte - 127)).  An MXFP8 matrix [rows][C] is two arrays: data uint8 [rows][ld] and scales uint8 [rows][ld / 32]; the
+ * columns [C, ld) hold zero elements.  Scale rule: the smallest power of two s with amax / s <= 448 (an all-zero block gets
+ * 2^-127), elements x / s rounded to nearest-even -- nothing saturates (tfimm/engine/pack.py mx_quantize is the reference).
+ * ======================================================================================= */
+
+/* tfimm_hip_quantize_mx: bf16 rows [rows][x_stride] -> MXFP8 rows (q [rows][ldq], q_scale [rows][ldq / 32]).
+ * gamma / beta (fp32 [C], both or neither): a LayerNormalization over the C channels is applied first -- the two-pass fp32
+ * statistics of tfimm_hip_row_stats, y = (x - mean) * rstd * gamma + beta -- so the normalised tensor is never written.
+ * C % 32 == 0, C <= 4096 (TFIMM_EUNSUP beyond), ldq % 32 == 0, x 16-byte aligned.
+ * Replaces, in the reference (fp8 mode): the LayerNormalization in front of a Dense layer
+ *     vit.py:222,231  swin.py:317,322  cait.py:186-190  convnext.py:226-228
+ * and the operand cast of a Dense layer whose input has no LayerNorm (attn/proj: vit.py:169, swin.py:197). */
+TFIMM_API int tfimm_hip_quantize_mx(const void* x, int64_t rows, int C, int64_t x_stride, const float* gamma,
+                                    const float* beta, float eps, void* q, void* q_scale, int ldq, void* stream);
+
+/* tfimm_hip_gemm_mx: out[M][N] = epilogue( deq(A)[M][K] . deq(W)[N][K]^T ), fp32 accumulation (v_mfma_scale_f32_32x32x64_f8f6f4).
+ *   A: MXFP8 [M][lda] + a_scale [M][lda / 32];  W: MXFP8 [N][ldw] + w_scale [N][ldw / 32] (tfimm/engine/pack.py pack_dense_mx)
+ *   K % 32 == 0, N % 32 == 0; lda, ldw multiples of 128 and >= K rounded up to 128, elements [K, that) zero.
+ *   epilogue as tfimm_hip_gemm: + bias[n], act unless act_after_res, + bf16 residual[m][n] (ldr), act if act_after_res;
+ *   stored as out_fmt 0 = bf16, 1 = fp32 ([M][ldc]) or 2 = MXFP8 (out [M][N] + out_scale [M][N / 32]; ldc == N, N % 128 == 0:
+ *   the result is quantized per 32-column block in the epilogue, the A operand of the next tfimm_hip_gemm_mx).
+ *   Offsets are 64-bit: any size that fits the int32 fields is accepted.
+ * Replaces, in the reference (fp8 mode): tf.keras.layers.Dense of the transformer blocks
+ *     vit.py:155,169  swin.py:167,197  cait.py:59-79  transformers.py:209-212  convnext.py:229-231
+ * and their residual adds (vit.py:228,234, swin.py:318,325, cait.py:187-190, convnext.py:232). */
+typedef struct tfimm_gemm_mx_desc {
+  const void* a;          /* e4m3 [M][lda]         */
+  const void* a_scale;    /* e8m0 [M][lda / 32]    */
+  const void* w;          /* e4m3 [N][ldw]         */
+  const void* w_scale;    /* e8m0 [N][ldw / 32]    */
+  const float* bias;      /* [N] or NULL           */
+  const void* residual;   /* bf16 [M][ldr] or NULL */
+  void* out;              /* bf16 / fp32 [M][ldc], or e4m3 [M][N] */
+  void* out_scale;        /* e8m0 [M][N / 32] (out_fmt 2), else ignored */
+  int32_t M, N, K;
+  int32_t lda, ldw, ldr, ldc;
+  int32_t out_fmt;        /* 0 bf16, 1 fp32, 2 MXFP8 */
+  int32_t act, act_after_res;
+} tfimm_gemm_mx_desc;
+TFIMM_API int tfimm_hip_gemm_mx(const tfimm_gemm_mx_desc* d, void* stream);
+
+/* =======================================================================================
  * FLOAT32 VERIFICATION PATH (csrc/ref32.hip; selected by TFIMM_PRECISION=fp32, tfimm/engine/precision.py)
  *
  * The reference is float32 end to end and pins values at 1e-3 relative to the maximum (tests/test_timm.py:71).  The

@@ -93,6 +93,7 @@ const std::map<std::string, Entry>& table() {
       TFIMM_ADAPTER_DESC(tfimm_hip_gemm, tfimm_gemm_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_conv_chain, tfimm_chain_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_mlp_fused, tfimm_mlp_desc),
+      TFIMM_ADAPTER_DESC(tfimm_hip_gemm_mx, tfimm_gemm_mx_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_expand_dwconv, tfimm_expand_dw_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_stem_conv_pool, tfimm_stem_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_attention, tfimm_attn_desc),
@@ -100,6 +101,7 @@ const std::map<std::string, Entry>& table() {
       TFIMM_ADAPTER(tfimm_hip_cast_input, vp, int, mp, int64_t, int, int),
       TFIMM_ADAPTER(tfimm_hip_cast_input_pad, vp, int, mp, int, int, int, int, int, int, int, int),
       TFIMM_ADAPTER(tfimm_hip_row_stats, vp, float*, int64_t, int, int64_t, float),
+      TFIMM_ADAPTER(tfimm_hip_quantize_mx, vp, int64_t, int, int64_t, fp, fp, float, mp, mp, int),
       TFIMM_ADAPTER(tfimm_hip_layernorm, vp, mp, fp, fp, int64_t, int, int64_t, int64_t, float),
       TFIMM_ADAPTER(tfimm_hip_class_attention, vp, vp, mp, int, int, int, int, int, int, int),
       TFIMM_ADAPTER(tfimm_hip_copy_rows, vp, mp, int, int, int, int, int),

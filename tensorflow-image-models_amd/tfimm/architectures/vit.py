@@ -200,7 +200,7 @@ class ViT(Model):
         if nt == 1:
             features = b.layernorm(x, "norm", eps, row_select=(0, 1), cite="vit.py:452,462", name="norm[cls]")
             if c.representation_size:
-                features = b.dense(features, "pre_logits/fc/kernel", "pre_logits/fc/bias", act="tanh",
+                features = b.dense(features, "pre_logits/fc/kernel", "pre_logits/fc/bias", act="tanh", mx=False,
                                    cite="vit.py:351-359,460")
         else:
             # x[:, :2] after the final LN, kept as one (B, 2*D) tensor (vit.py:458)

@@ -103,6 +103,15 @@ class MlpDesc(C.Structure):
                 ("C", C.c_int32), ("hidden", C.c_int32), ("act", C.c_int32), ("eps", C.c_float)]
 
 
+class GemmMxDesc(C.Structure):
+    """tfimm_gemm_mx_desc: the MXFP8 GEMM of the fp8 precision mode (csrc/mx.hip)"""
+    _fields_ = [("a", C.c_void_p), ("a_scale", C.c_void_p), ("w", C.c_void_p), ("w_scale", C.c_void_p),
+                ("bias", C.c_void_p), ("residual", C.c_void_p), ("out", C.c_void_p), ("out_scale", C.c_void_p),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("lda", C.c_int32), ("ldw", C.c_int32), ("ldr", C.c_int32), ("ldc", C.c_int32),
+                ("out_fmt", C.c_int32), ("act", C.c_int32), ("act_after_res", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tfimm_hip.h
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -112,6 +121,8 @@ SYMBOLS = {
     "tfimm_hip_gemm": (_i, [C.POINTER(GemmDesc), _vp]),
     "tfimm_hip_conv_chain": (_i, [C.POINTER(ChainDesc), _vp]),
     "tfimm_hip_mlp_fused": (_i, [C.POINTER(MlpDesc), _vp]),
+    "tfimm_hip_gemm_mx": (_i, [C.POINTER(GemmMxDesc), _vp]),
+    "tfimm_hip_quantize_mx": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _f, _vp, _vp, _i, _vp]),
     "tfimm_hip_expand_dwconv": (_i, [C.POINTER(ExpandDwDesc), _vp]),
     "tfimm_hip_stem_conv_pool": (_i, [C.POINTER(StemDesc), _vp]),
     "tfimm_hip_cast_input": (_i, [_vp, _i, _vp, _i64, _i, _i, _vp]),

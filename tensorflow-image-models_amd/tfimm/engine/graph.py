@@ -33,17 +33,24 @@ class TRef:
     C: int
     H: int = 0
     W: int = 0
-    dtype: str = "bf16"    # "bf16" | "f32"
+    dtype: str = "bf16"    # "bf16" | "f32" | "mx" (MXFP8: e4m3 [rows][mx_ld] followed by E8M0 scales [rows][mx_ld / 32])
     keep: bool = False     # never recycle the buffer (outputs / returned features)
     # a view onto another tensor's buffer: (parent id, element offset per image-row stride)
     name: str = ""
 
     @property
     def itemsize(self) -> int:
-        return 2 if self.dtype == "bf16" else 4
+        return {"bf16": 2, "f32": 4, "mx": 1}[self.dtype]
+
+    @property
+    def mx_ld(self) -> int:
+        """MXFP8 tensors: row length of the element array (C zero padded to the K-tile of tfimm_hip_gemm_mx)"""
+        return pack.ceil_to(self.C, pack.MX_KPAD)
 
     @property
     def bytes_per_image(self) -> int:
+        if self.dtype == "mx":
+            return self.rows * (self.mx_ld + self.mx_ld // pack.MX_BLOCK)
         return self.rows * self.C * self.itemsize
 
 
@@ -115,7 +122,7 @@ class Program:
         total = 0
         for op in self.ops:
             a = op.attrs
-            if op.kind in ("gemm", "stem_pool"):
+            if op.kind in ("gemm", "gemm_mx", "stem_pool"):
                 total += 2 * a["M"] * a["N"] * a["K_true"]
             elif op.kind in ("attention", "talking_heads_attention", "conv_chain", "mlp_fused"):
                 total += a["flops"]
@@ -202,6 +209,31 @@ class Program:
     def make_plan(self, batch: int, device: str = "cuda") -> "Plan":
         return Plan(self, batch, device)
 
+    def fuse_mx_outputs(self) -> int:
+        """fp8 mode: a gemm_mx whose bf16 result is read only by a quant_mx without LayerNorm (fc1 -> fc2) writes MXFP8
+        itself -- quantized per 32-column block in its epilogue -- and the quantize pass disappears: the 4C-wide hidden
+        tensor moves 1 byte per element instead of 2 + 2 + 1.  Returns the number of fused pairs."""
+        readers: Dict[int, List[int]] = {}
+        for i, op in enumerate(self.ops):
+            for t in op.inputs:
+                readers.setdefault(t, []).append(i)
+        drop = set()
+        for op in self.ops:
+            if op.kind != "gemm_mx" or op.attrs["out_fmt"] != 0:
+                continue
+            t = self.tensors[op.output]
+            r = readers.get(t.id, [])
+            if t.keep or len(r) != 1:
+                continue
+            q = self.ops[r[0]]
+            if q.kind != "quant_mx" or q.attrs["ln"] or t.C % pack.MX_KPAD:
+                continue
+            op.output = q.output
+            op.attrs["out_fmt"] = 2
+            drop.add(r[0])
+        self.ops = [op for i, op in enumerate(self.ops) if i not in drop]
+        return len(drop)
+
     def live_across(self, op_index: int) -> List[int]:
         """Tensors written by ops [0, op_index) that ops [op_index, ...) still read (or that are program outputs)."""
         written, needed = set(), set()
@@ -246,6 +278,13 @@ class Builder:
         self._orig_w = weights
         self.p = Program()
         self.fp32 = self.p.precision == "fp32"      # verification path: no cross-layer fusion, unrounded weights
+        self.fp8 = self.p.precision == "fp8"        # MXFP8 Dense layers (engine/precision.py)
+
+    def finish(self) -> Program:
+        """End of lowering: program-level rewrites that need every reader of a tensor to be known."""
+        if self.fp8:
+            self.p.fuse_mx_outputs()
+        return self.p
 
     # -- weights ---------------------------------------------------------------------------
     def wget(self, name: str) -> np.ndarray:
@@ -561,8 +600,11 @@ class Builder:
               in_cols: Optional[Tuple[int, int]] = None,
               out: Optional[TRef] = None, out_col: int = 0, out_scale: Optional[str] = None,
               residual_row: Optional[int] = None, out_row: Optional[int] = None,
-              ln: Optional[Tuple[str, float, TRef]] = None, cite="", name="") -> TRef:
+              ln: Optional[Tuple[str, float, TRef]] = None, mx: bool = True, cite="", name="") -> TRef:
         """tf.keras.layers.Dense (+ activation, + residual add).
+
+        fp8 mode (engine/precision.py): a layer ``mx_eligible`` accepts runs as quant_mx + gemm_mx (csrc/mx.hip); ``mx=False``
+        keeps a layer in bf16 (classifier-side layers such as pre_logits).
 
         ``ln=(prefix, eps, stats)``: ``x`` is the RAW input of LayerNormalization ``prefix`` whose output this layer reads;
         the normalisation is folded into the layer (gamma into the weights, beta . W into the bias, per-row mean / rstd
@@ -594,6 +636,9 @@ class Builder:
             assert kin == x.C, f"{kernel}: in={kin} but tensor has C={x.C}"
         else:
             assert in_cols[1] == kin and in_cols[0] + kin <= x.C
+        if mx and ln is None and self.mx_eligible(x, kin, kout) and not out_f32 and row_select is None and in_cols is None \
+                and out is None and residual_row is None and out_row is None:
+            return self._dense_mx(x, k, bvec_in, kernel, act=act, residual=residual, cite=cite, name=name)
         if ln is not None:
             assert residual is None and row_select is None and in_cols is None and not out_f32 and out is None
             assert kin % 8 == 0 and kout % 8 == 0
@@ -646,6 +691,40 @@ class Builder:
         p.add("gemm", ins, out, consts, cite=cite, **attrs)
         return out
 
+    def mx_eligible(self, x: TRef, kin: int, kout: int) -> bool:
+        """fp8 mode: a Dense layer over the bf16 tensor x runs on MXFP8 operands (K and N multiples of 32, rows the quantize
+        kernel takes); everything else stays bf16."""
+        return (self.fp8 and x.dtype == "bf16" and kin == x.C and kin % pack.MX_BLOCK == 0 and kout % pack.MX_BLOCK == 0
+                and kin <= 4096)
+
+    def _dense_mx(self, x: TRef, k: np.ndarray, bvec: Optional[np.ndarray], kernel: str, *, act="",
+                  residual: Optional[TRef] = None, ln: Optional[Tuple[str, float]] = None, cite="", name="") -> TRef:
+        """quant_mx (x -> MXFP8, through LayerNormalization ``ln=(prefix, eps)`` first if given) + gemm_mx over the host-quantized
+        weights (pack.pack_dense_mx; unfolded: the LayerNorm is applied by the quantize pass).  Program.fuse_mx_outputs later
+        lets an fc1 whose only reader is such a layer write MXFP8 itself."""
+        p = self.p
+        kin, kout = k.shape
+        q = p.new_tensor(x.rows, kin, x.H, x.W, dtype="mx", name=(name or kernel) + ":mx_in")
+        qc, qa = {}, dict(rows=x.rows, C=kin, ln=False, eps=0.0)
+        if ln is not None:
+            qc = {"gamma": p.new_const(self.wget(ln[0] + "/gamma"), ln[0] + "/gamma"),
+                  "beta": p.new_const(self.wget(ln[0] + "/beta"), ln[0] + "/beta")}
+            qa.update(ln=True, eps=float(ln[1]))
+        p.add("quant_mx", [x], q, qc, cite=cite, **qa)
+        w, ws = pack.pack_dense_mx(k)
+        consts = {"w": p.new_const(w, kernel + ":mx"), "w_scale": p.new_const(ws, kernel + ":mx_scale")}
+        if bvec is not None:
+            consts["bias"] = p.new_const(np.ascontiguousarray(bvec, dtype=np.float32), kernel + ":bias")
+        sp = (x.H, x.W) if x.H * x.W == x.rows else (0, 0)
+        out = p.new_tensor(x.rows, kout, sp[0], sp[1], name=name or kernel)
+        ins = [q]
+        attrs = dict(M=x.rows, N=kout, K=kin, K_true=kin, act=act, out_fmt=0, has_residual=residual is not None)
+        if residual is not None:
+            assert residual.C == kout and residual.rows == x.rows and residual.dtype == "bf16"
+            ins.append(residual)
+        p.add("gemm_mx", ins, out, consts, cite=cite, **attrs)
+        return out
+
     def empty(self, rows: int, C: int, dtype="bf16", name="") -> TRef:
         return self.p.new_tensor(rows, C, dtype=dtype, name=name)
 
@@ -662,6 +741,11 @@ class Builder:
         """LayerNormalization(ln_prefix) followed by a Dense layer that is its only reader: folded into one GEMM over the raw
         rows + a statistics pass when the row width allows (``can_fold_ln``), the two launches otherwise."""
         kshape = self.wget(kernel).shape
+        if self.mx_eligible(x, kshape[-2], kshape[-1]):
+            k = self.wget(kernel)
+            k = k[0, 0] if k.ndim == 4 else k
+            return self._dense_mx(x, k, None if bias is None else self.wget(bias), kernel, act=act,
+                                  ln=(ln_prefix, eps), cite=(cite_ln + ", " + cite) if cite_ln else cite)
         if self.can_fold_ln(x) and kshape[-1] % 8 == 0:      # the folded epilogue stores whole 16-byte groups
             return self.dense(x, kernel, bias, act=act, ln=(ln_prefix, eps, self.row_stats(x, eps, cite=cite_ln)),
                               cite=(cite_ln + ", " + cite) if cite_ln else cite)
@@ -672,8 +756,8 @@ class Builder:
         """residual + [out_scale *] fc2(act(fc1(LayerNormalization(x)))) as ONE launch (tfimm_hip_mlp_fused: the 4C-wide hidden
         tensor stays in registers).  ``fc1`` / ``fc2`` are layer prefixes (kernel + bias).  Returns None when the shape is
         not one the kernel is built for (C = 128, hidden = 512) -- the caller lowers the two GEMMs."""
-        if self.fp32 or os.environ.get("TFIMM_NO_MLP_FUSION"):
-            return None
+        if self.fp32 or self.fp8 or os.environ.get("TFIMM_NO_MLP_FUSION"):
+            return None      # (fp8: the two Dense layers run as MXFP8 GEMMs)
         k1, k2 = self.wget(fc1 + "/kernel"), self.wget(fc2 + "/kernel")
         if k1.ndim == 4:     # ConvMLP: 1x1 convolutions (layers/transformers.py:238-252)
             k1, k2 = k1[0, 0], k2[0, 0]
@@ -1070,6 +1154,11 @@ class Plan:
             return self.external[tid]
         return self.slabs[self.assign[tid]].data_ptr()
 
+    def mx_ptrs(self, t: TRef) -> Tuple[int, int]:
+        """(elements, scales) of an MXFP8 tensor: the scale array follows the batch's element array in the same slab"""
+        base = self.tptr(t.id)
+        return base, base + self.batch * t.rows * t.mx_ld
+
     def cptr(self, cid: Optional[int]) -> Optional[int]:
         if cid is None:
             return None
@@ -1162,6 +1251,31 @@ class Plan:
                 self._gemm_descs.append(d)
                 self._gemm_call_index.append(len(self.calls))
                 self.calls.append((lib.tfimm_hip_gemm, (C.byref(d),)))
+            elif k == "quant_mx":
+                x_t, q_t = prog.tensors[op.inputs[0]], prog.tensors[op.output]
+                q, qs = self.mx_ptrs(q_t)
+                self.calls.append((lib.tfimm_hip_quantize_mx,
+                                   (self.tptr(x_t.id), B * a["rows"], a["C"], x_t.C, self.cptr(op.consts.get("gamma")),
+                                    self.cptr(op.consts.get("beta")), a["eps"], q, qs, q_t.mx_ld)))
+            elif k == "gemm_mx":
+                d = ffi.GemmMxDesc()
+                a_t, out_t = prog.tensors[op.inputs[0]], prog.tensors[op.output]
+                d.a, d.a_scale = self.mx_ptrs(a_t)
+                d.w, d.w_scale = self.cptr(op.consts["w"]), self.cptr(op.consts["w_scale"])
+                d.bias = self.cptr(op.consts.get("bias"))
+                if a["out_fmt"] == 2:
+                    d.out, d.out_scale = self.mx_ptrs(out_t)
+                else:
+                    d.out = self.tptr(out_t.id)
+                d.M, d.N, d.K = a["M"] * B, a["N"], a["K"]
+                d.lda, d.ldw, d.ldc = a_t.mx_ld, pack.ceil_to(a["K"], pack.MX_KPAD), out_t.C
+                d.out_fmt = a["out_fmt"]
+                d.act, d.act_after_res = ffi.ACT[a["act"]], 0
+                if a["has_residual"]:
+                    d.residual = self.tptr(op.inputs[1])
+                    d.ldr = prog.tensors[op.inputs[1]].C
+                self._keepalive.append(d)
+                self.calls.append((lib.tfimm_hip_gemm_mx, (C.byref(d),)))
             elif k == "conv_chain":
                 d = ffi.ChainDesc()
                 d.x = self.tptr(op.inputs[0])
@@ -1458,7 +1572,7 @@ class Plan:
         exactly the launches this plan would (bit-identical results)."""
         import struct
         import torch
-        if self.prog.precision != "bf16":
+        if self.prog.precision == "fp32":
             raise NotImplementedError("plans of the float32 verification path are not exported")
         if self.device == "cpu":
             raise RuntimeError("export needs a plan built on the GPU (tile hints and occupancy are resolved there)")

@@ -62,6 +62,78 @@ def pack_dense(kernel: np.ndarray, bias: Optional[np.ndarray], fp32: bool = Fals
     return wt, b
 
 
+# ---- MXFP8 (OCP microscaling: e4m3fn elements in blocks of 32 along K, one E8M0 scale per block) ------------------------
+MX_BLOCK = 32
+MX_KPAD = 128        # K-tile of tfimm_hip_gemm_mx: rows of MX operands are zero padded to a multiple of it
+E4M3_MAX = 448.0
+
+
+def mx_scale_exp(amax: np.ndarray) -> np.ndarray:
+    """The scale rule: exponent k of the smallest power of two s = 2^k with amax / s <= 448, at least -127 (an all-zero
+    block gets 2^-127).  amax = 1.m * 2^e  ->  k = e - 8, plus one when 1.m > 1.75 (448 = 1.75 * 2^8)."""
+    u = np.ascontiguousarray(amax, dtype=np.float32).view(np.uint32).astype(np.int64)
+    k = (u >> 23) - 135 + ((u & 0x7FFFFF) > 0x600000)
+    return np.maximum(k, -127)
+
+
+def e4m3_encode(v: np.ndarray) -> np.ndarray:
+    """fp32 (|v| <= 448) -> e4m3fn codes (uint8), round to nearest even, subnormals included; a zero keeps the sign of v.
+    (Not ``torch.Tensor.to(float8_e4m3fn)``: that turns values above 448 into NaN.)"""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    sign = ((v.view(np.uint32) >> 24) & 0x80).astype(np.uint32)
+    a = np.abs(v)
+    sub = np.rint(a * np.float32(512.0)).astype(np.uint32)         # multiples of 2^-9; 8 = 2^-6 continues into the normals
+    au = a.view(np.uint32).astype(np.uint64)
+    au = au + 0x7FFFF + ((au >> 20) & 1)
+    nrm = ((au >> 20).astype(np.int64) - (120 << 3)).astype(np.int64)
+    code = np.where(a < np.float32(0.015625), sub.astype(np.int64), nrm)
+    return (sign.astype(np.int64) | code).astype(np.uint8)
+
+
+def e4m3_decode(c: np.ndarray) -> np.ndarray:
+    """e4m3fn codes -> fp32 values (0x7f / 0xff, the NaN codes, never occur in MX data produced here)."""
+    c = np.asarray(c, dtype=np.uint8).astype(np.int64)
+    e, m = (c >> 3) & 15, c & 7
+    mag = np.where(e == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * np.exp2(e - 7.0))
+    return np.where(c & 0x80, -mag, mag).astype(np.float32)
+
+
+def mx_quantize(x: np.ndarray):
+    """The MXFP8 reference quantizer every test and the weight packer share (csrc/mx.hip implements the same rule):
+    x [..., K] fp32 with K % 32 == 0 -> (codes uint8 [..., K], scale bytes uint8 [..., K / 32]); element = x / 2^k rounded
+    to nearest-even in e4m3fn, scale byte = k + 127."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    assert x.shape[-1] % MX_BLOCK == 0, x.shape
+    blk = x.reshape(x.shape[:-1] + (x.shape[-1] // MX_BLOCK, MX_BLOCK))
+    k = mx_scale_exp(np.abs(blk).max(axis=-1))
+    inv = ((127 - k).astype(np.uint32) << 23).view(np.float32)      # 2^-k, a normal float for every k the rule gives
+    codes = e4m3_encode(blk * inv[..., None]).reshape(x.shape)
+    return codes, (k + 127).astype(np.uint8)
+
+
+def mx_dequantize(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """(codes [..., K], scale bytes [..., >= K / 32]) -> fp64 values [..., K]."""
+    v = e4m3_decode(codes).astype(np.float64)
+    k = codes.shape[-1]
+    s = np.exp2(scales[..., : k // MX_BLOCK].astype(np.float64) - 127.0)
+    return (v.reshape(v.shape[:-1] + (k // MX_BLOCK, MX_BLOCK)) * s[..., None]).reshape(v.shape)
+
+
+def pack_dense_mx(kernel: np.ndarray):
+    """Keras Dense kernel (in = K, out = N) -> (W e4m3 codes uint8 [N][Kp], E8M0 scales uint8 [N][Kp / 32]), Kp = K rounded up
+    to 128: each output column is quantized along K in blocks of 32 (mx_quantize); the padding is zero elements with scale
+    byte 0."""
+    kin, kout = kernel.shape
+    assert kin % MX_BLOCK == 0, kernel.shape
+    kp = ceil_to(kin, MX_KPAD)
+    codes, scales = mx_quantize(np.ascontiguousarray(np.asarray(kernel, dtype=np.float32).T))
+    w = np.zeros((kout, kp), dtype=np.uint8)
+    w[:, :kin] = codes
+    ws = np.zeros((kout, kp // MX_BLOCK), dtype=np.uint8)
+    ws[:, : kin // MX_BLOCK] = scales
+    return w, ws
+
+
 def pack_conv(kernel: np.ndarray, scale: Optional[np.ndarray], shift: Optional[np.ndarray],
               cin_stored: int, fp32: bool = False):
     """HWIO conv kernel -> (Wt, bias, K, mode).

@@ -184,7 +184,7 @@ class Model:
             b = Builder(self._weights)
             b.p.const_cache = self._const_cache
             self.lower(b, H, W, want_features)
-            self._programs[key] = b.p
+            self._programs[key] = b.finish()
         return self._programs[key]
 
     # -- forward ---------------------------------------------------------------------------------
