@@ -68,14 +68,14 @@ __global__ void __launch_bounds__(256) quantize_mx_kernel(const bf16_t* __restri
     unpack8(u, v[i]);
   }
   if (LN) {
-    // the two-pass fp32 statistics of tfimm_hip_row_stats (mean, then the mean square deviation; rsqrt)
-    const float inv_d = 1.f / (float)C;
+    // two-pass fp32 statistics (mean, then the mean square deviation; rsqrt).  Both are divided by C, not multiplied by a
+    // rounded 1 / C: the mean of a constant row is then its value exactly (C * x is exact in fp32), so y == beta
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
       for (int e = 0; e < 8; ++e) sum += v[i][e];
-    const float mean = wave_sum(sum) * inv_d;
+    const float mean = wave_sum(sum) / (float)C;
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(256) quantize_mx_kernel(const bf16_t* __restri
           sq += t * t;
         }
       }
-    const float rstd = rsqrtf(wave_sum(sq) * inv_d + eps);
+    const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int c = lane + 64 * i;

@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import mx_checks as mxc
 import test_architectures  # noqa: F401
 import tfimm
 from tfimm.engine import ffi, pack, precision
@@ -227,3 +228,145 @@ def test_bad_mx_descriptors_are_refused_without_a_gpu():
     assert q(p, 4, 64, 64, p, None, 1e-6, p, p, 64, None) == -1          # gamma without beta
     assert q(p, 4, 8192, 8192, None, None, 0.0, p, p, 8192, None) == -2  # beyond 4096 channels: TFIMM_EUNSUP
     assert b"quantize_mx" in lib.tfimm_hip_last_error()
+
+
+# ---- the LayerNorm bar of tfimm_hip_quantize_mx bites (tests/mx_checks.py; the GPU cases are in test_gpu_fp8.py) -----------
+def ln_rows(rows, C, seed):
+    """bf16 rows of mixed sigma (2^-12 .. 2^4), a quarter of them far from zero (mean 2^5 .. 2^9 sigma), a constant row and
+    an all-zero row; gamma of mixed magnitude with whole zero blocks (beta zero there too: scale byte 0)"""
+    rng = np.random.default_rng(seed)
+    sig = np.exp2(rng.uniform(-12, 4, (rows, 1)))
+    mu = sig * rng.standard_normal((rows, 1))
+    far = rng.random((rows, 1)) < 0.25
+    mu = np.where(far, sig * np.exp2(rng.uniform(5, 9, (rows, 1))) * np.sign(rng.standard_normal((rows, 1))), mu)
+    x = mu + sig * rng.standard_normal((rows, C))
+    x[1] = 3.0 * rng.standard_normal()
+    x[2] = 0.0
+    x = pack.bf16_bits_to_f32(pack.to_bf16_bits(x.astype(np.float32)))
+    gamma = (rng.standard_normal(C) * np.exp2(rng.integers(-3, 2, C))).astype(np.float32)
+    beta = (rng.standard_normal(C) * 0.5).astype(np.float32)
+    for b in rng.choice(C // 32, max(1, C // 256), replace=False):
+        gamma[32 * b:32 * b + 32] = 0.0
+        beta[32 * b:32 * b + 32] = 0.0
+    return x, gamma, beta
+
+
+def ln_quantize_model(x, gamma, beta, eps, defect=None):
+    """numpy model of tfimm_hip_quantize_mx with LayerNorm: fp32 two-pass statistics (pairwise sums: another order than the
+    kernel's), mean = sum / C, rstd = 1 / sqrt(var + eps), y = fma((x - mean) * rstd, gamma, beta) (one rounding), then the
+    shared quantizer.  ``defect`` models a wrong kernel."""
+    f = np.float32
+    x = np.asarray(x, f)
+    C = x.shape[-1]
+    s = x.sum(-1, dtype=f, keepdims=True)
+    if defect == "padded_mean":
+        mean = s / f(512 * -(-C // 512))                      # divided by the register width of the row
+    elif defect == "reciprocal_mean":
+        mean = s * (f(1) / f(C))                              # rounded 1 / C: a constant row's mean may miss its value
+    else:
+        mean = s / f(C)
+    if defect == "one_pass":
+        var = (x * x).sum(-1, dtype=f, keepdims=True) / f(C) - mean * mean
+    else:
+        d = x - mean
+        var = (d * d).sum(-1, dtype=f, keepdims=True) / f(C)
+    e = f({"no_eps": 0.0, "eps_1e-5": 1e-5}.get(defect, eps))
+    if defect == "eps_on_sigma":
+        rstd = f(1) / (np.sqrt(np.maximum(var, f(0))) + e)
+    else:
+        rstd = f(1) / np.sqrt(np.maximum(var + e, f(0)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n = ((x - mean) * rstd).astype(np.float64)
+    y = n * gamma + (0.0 if defect == "no_beta" else beta.astype(np.float64))
+    return pack.mx_quantize(y.astype(np.float32))
+
+
+LN_CPU_CASES = [(256, 96, 1e-6), (253, 480, 1e-6), (256, 768, 1e-6), (97, 4096, 1e-6), (256, 384, 1e-5)]
+# least share of elements each defect must break, per case (the measured share is several times larger)
+LN_DEFECTS = {"no_eps": 0.05, "eps_1e-5": 0.05, "eps_on_sigma": 0.05, "one_pass": 0.0008, "padded_mean": 0.2,
+              "no_beta": 0.3}
+
+
+@pytest.mark.parametrize("rows,C,eps", LN_CPU_CASES)
+def test_ln_quantize_bar_passes_the_honest_kernel(rows, C, eps):
+    x, g, b = ln_rows(rows, C, C)
+    c, s = ln_quantize_model(x, g, b, eps)
+    bad, exempt = mxc.check_ln_quantize(c, s, x, g, b, eps)
+    assert bad == 0 and exempt <= mxc.LN_EXEMPT_CAP, (bad, exempt)
+    # constant and all-zero rows: y == beta exactly
+    ref_c, ref_s = pack.mx_quantize(np.tile(b, (2, 1)))
+    np.testing.assert_array_equal(c[1:3], ref_c)
+    np.testing.assert_array_equal(s[1:3], ref_s)
+
+
+# not defects: the register width of a 4096-channel row is 4096; eps 1e-5 where the layer's eps is 1e-5
+LN_DEFECT_CASES = [(case, d) for case in LN_CPU_CASES for d in sorted(LN_DEFECTS)
+                   if not (d == "padded_mean" and case[1] % 512 == 0) and not (d == "eps_1e-5" and case[2] == 1e-5)]
+
+
+@pytest.mark.parametrize("case,defect", LN_DEFECT_CASES)
+def test_ln_quantize_bar_rejects_defects(case, defect):
+    rows, C, eps = case
+    x, g, b = ln_rows(rows, C, C)
+    with np.errstate(all="ignore"):
+        c, s = ln_quantize_model(x, g, b, eps, defect)
+    bad, _ = mxc.check_ln_quantize(c, s, x, g, b, eps)
+    assert bad > LN_DEFECTS[defect] * c.size, (defect, bad / c.size)
+
+
+def test_ln_quantize_mean_through_a_rounded_reciprocal_misses_constant_rows():
+    """the quantize kernel's statistics before this bar: sum * fl(1 / C).  At C = 480 the mean of most constant bf16 rows is
+    then not their value, and y != beta"""
+    x = np.tile(pack.bf16_bits_to_f32((np.arange(0x3F80, 0x4000, dtype=np.uint16))).reshape(-1, 1), (1, 480))
+    g = np.ones(480, np.float32)
+    b = np.linspace(-1, 1, 480, dtype=np.float32)
+    want_c, want_s = pack.mx_quantize(np.tile(b, (len(x), 1)))
+    c, s = ln_quantize_model(x, g, b, 1e-6)
+    np.testing.assert_array_equal(c, want_c)
+    np.testing.assert_array_equal(s, want_s)
+    c, s = ln_quantize_model(x, g, b, 1e-6, "reciprocal_mean")
+    assert (c != want_c).any(axis=1).mean() > 0.5
+
+
+# ---- the gemm_mx bars bite (mx_checks.gemm_tol / check_mxfp8_output, shared with test_gpu_fp8.py) -------------------------
+def _gemm_mx_model(M, N, K, seed, act="gelu", kernel_act=None, drop_bias=False, drop_residual=False):
+    """fp64 reference v of act(A W^T + b) + r over dequantized MX operands, its bar, and an honest kernel's fp32 result:
+    the reference perturbed by a third of the accumulation bar and rounded to fp32 (``kernel_act`` / ``drop_*``: defects)"""
+    from scipy.special import erf
+    rng = np.random.default_rng(seed)
+    a_c, a_s = pack.mx_quantize((rng.standard_normal((M, K)) * np.exp2(rng.integers(-3, 3, (M, 1)))).astype(np.float32))
+    w_c, w_s = pack.mx_quantize((rng.standard_normal((N, K)) * 0.05).astype(np.float32))
+    A, Wd = pack.mx_dequantize(a_c, a_s), pack.mx_dequantize(w_c, w_s)
+    b = rng.standard_normal(N).astype(np.float32)
+    r = pack.bf16_bits_to_f32(pack.to_bf16_bits(rng.standard_normal((M, N)).astype(np.float32)))
+    acts = {"": lambda v: v, "gelu": lambda v: 0.5 * v * (1 + erf(v / np.sqrt(2))),
+            "gelu_tanh": lambda v: 0.5 * v * (1 + np.tanh(np.sqrt(2 / np.pi) * (v + 0.044715 * v ** 3)))}
+    acc = A @ Wd.T
+    mag = np.abs(A) @ np.abs(Wd).T
+    v = acts[act](acc + b) + r
+    tol = mxc.gemm_tol(mag, v, act, b, r)
+    got = acts[kernel_act or act](acc * (1 + 1e-6) + (0 if drop_bias else b)) + (0 if drop_residual else r)
+    got = got + tol / 3 * rng.uniform(-1, 1, got.shape)
+    return got.astype(np.float32).astype(np.float64), v, tol
+
+
+def test_gemm_mx_bars_pass_the_honest_kernel_and_reject_defects():
+    got, v, tol = _gemm_mx_model(192, 256, 384, 0)
+    assert np.all(np.abs(got - v) <= tol)
+    g16 = pack.bf16_bits_to_f32(pack.to_bf16_bits(got.astype(np.float32))).astype(np.float64)
+    assert np.all(np.abs(g16 - v) <= mxc.bf16_tol(v, tol))
+    for defect in ({"drop_bias": True}, {"drop_residual": True}):
+        got, v, tol = _gemm_mx_model(192, 256, 384, 0, **defect)
+        g16 = pack.bf16_bits_to_f32(pack.to_bf16_bits(got.astype(np.float32))).astype(np.float64)
+        assert (np.abs(g16 - v) > mxc.bf16_tol(v, tol)).mean() > 0.5, defect
+
+
+def test_mxfp8_output_bar_passes_the_honest_kernel_and_rejects_tanh_gelu():
+    got, v, tol = _gemm_mx_model(333, 384, 96, 1)
+    c, s = pack.mx_quantize(got.astype(np.float32))
+    fails, worst = mxc.check_mxfp8_output(c, s, v, tol)
+    assert not fails and worst <= 1.0, fails
+    got, v, tol = _gemm_mx_model(333, 384, 96, 1, kernel_act="gelu_tanh")
+    c, s = pack.mx_quantize(got.astype(np.float32))
+    fails, _ = mxc.check_mxfp8_output(c, s, v, tol)
+    assert fails, "a tanh-form GELU passed the MXFP8 output bar"

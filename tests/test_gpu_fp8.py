@@ -1,12 +1,14 @@
 """pytest -m gpu: the MXFP8 precision mode (engine/precision.py "fp8", csrc/mx.hip).
 
 * tfimm_hip_quantize_mx is bit-exact against the shared numpy quantizer (engine/pack.py mx_quantize), with and without the
-  LayerNorm it can apply first;
+  LayerNorm it can apply first; with LayerNorm also against the fp64 LayerNorm on every row width class, exact except where
+  provably ambiguous (tests/mx_checks.py);
 * tfimm_hip_gemm_mx against an fp64 product of the DEQUANTIZED operands, every epilogue and output format, with a bar on
   fp32 accumulation only;
 * models: ViT / DeiT against an MX-emulated oracle (oracle.common.W.dense wrapped here so that it quantizes x and the kernel
   with the same rule), Swin / CaiT / ConvNeXt against the plain fp32 oracle next to the bf16 path's own deviation; every
   bar, and every observed deviation from the fp32 oracle, is recorded in tests/golden/fp8_bars.json;
+* every quant_mx / gemm_mx op of five fp8 programs, each against a reference built from its own read-back inputs;
 * eager vs graph replay, branches=2 vs branches=1, ResNet-50 under fp8 == bf16, an exported fp8 plan through the C host."""
 import contextlib
 import ctypes as C
@@ -19,6 +21,7 @@ import pytest
 import torch
 
 import model_checks as mc
+import mx_checks as mxc
 import oracle
 import oracle.common
 import test_architectures  # noqa: F401
@@ -97,14 +100,30 @@ def test_quantize_mx_with_layernorm_bit_exact(rows, c):
     np.testing.assert_array_equal(q, wq)
 
 
-def _e4m3_step(y):
-    a = np.abs(y)
-    return np.where(a < 2.0 ** -6, 2.0 ** -9, np.exp2(np.floor(np.log2(np.maximum(a, 2.0 ** -6))) - 3))
+LN_GPU_CASES = [(rows, c, eps) for rows, c in [(37, 32), (130, 96), (19, 192), (66, 384), (5, 480), (43, 544), (130, 768),
+                                                 (7, 1536), (9, 2560), (13, 4096)] for eps in (1e-5, 1e-6)]
+
+
+@pytest.mark.parametrize("rows,c,eps", LN_GPU_CASES)
+def test_quantize_mx_with_layernorm_against_fp64(rows, c, eps):
+    """mixed-sigma, far-from-zero, constant and zero rows (test_fp8.ln_rows), rows not a multiple of 4, ldq > C: exact
+    against the fp64 LayerNorm except where provably ambiguous (mx_checks.check_ln_quantize), y == beta on constant rows"""
+    from test_fp8 import ln_rows
+    x, g, b = ln_rows(rows, c, c + int(eps * 1e7))
+    ldq = pack.ceil_to(c, 128) + 128
+    q, s = _quantize_dev(x, ldq, g, b, eps)
+    bad, exempt = mxc.check_ln_quantize(q, s, x, g, b, eps)
+    assert bad == 0 and exempt <= mxc.LN_EXEMPT_CAP, (bad, exempt)
+    want_c, want_s = pack.mx_quantize(np.tile(b, (2, 1)))
+    np.testing.assert_array_equal(q[1:3, :c], want_c)                       # constant and all-zero rows: y == beta
+    np.testing.assert_array_equal(s[1:3, : c // 32], want_s)
+    assert (s[:, : c // 32][:, np.all(g.reshape(-1, 32) == 0, -1)] == 0).all()   # gamma = beta = 0: scale byte 0
+    assert not q[:, c:].any() and not s[:, c // 32:].any()                  # zero padding up to ldq
 
 
 def _gelu(v):
-    from math import erf, sqrt
-    return 0.5 * v * (1.0 + np.vectorize(erf)(v / sqrt(2.0)))
+    from scipy.special import erf
+    return 0.5 * v * (1.0 + erf(v / np.sqrt(2.0)))
 
 
 def _act(v, act):
@@ -112,15 +131,29 @@ def _act(v, act):
             "sigmoid": 1 / (1 + np.exp(-v)), "relu6": np.clip(v, 0, 6), "tanh": np.tanh(v)}[act]
 
 
-def _gemm_case(M, N, K, *, bias=True, act="", residual=False, act_after_res=False, out_fmt=0, seed=0):
+def _spread_blocks(rng, x, lo=-20, hi=20):
+    """every 32-block along the last axis of x with its own power-of-two scale in 2^lo .. 2^hi, and zero blocks in the
+    middle of K: scale bytes far from 127 on both sides, and 0"""
+    nb = x.shape[-1] // 32
+    e = rng.integers(lo, hi + 1, x.shape[:-1] + (nb, 1)).astype(np.float64)
+    e[rng.random(e.shape) < 0.05] = -np.inf
+    e[..., nb // 2, :] = -np.inf                                            # a zero block in the middle of K
+    return (x.reshape(x.shape[:-1] + (nb, 32)) * np.exp2(e)).reshape(x.shape).astype(np.float32)
+
+
+def _gemm_case(M, N, K, *, bias=True, act="", residual=False, act_after_res=False, out_fmt=0, seed=0, spread=False):
     rng = np.random.default_rng(seed + M + N + K)
     kp = pack.ceil_to(K, 128)
     a_f = (rng.standard_normal((M, K)) * np.exp2(rng.integers(-3, 3, (M, 1)))).astype(np.float32)
+    if spread:
+        a_f = _spread_blocks(rng, a_f)
     a_q, a_s = pack.mx_quantize(a_f)
     a = np.zeros((M, kp), np.uint8); a[:, :K] = a_q
     a_sc = np.zeros((M, kp // 32), np.uint8); a_sc[:, : K // 32] = a_s
     # an asymmetric weight (columns of different magnitude) catches a row <-> column swap of the lane maps
     w_f = (rng.standard_normal((K, N)) * 0.05 * (1 + np.arange(N) / N)).astype(np.float32)
+    if spread:
+        w_f = np.ascontiguousarray(_spread_blocks(rng, np.ascontiguousarray(w_f.T)).T)
     w, w_sc = pack.pack_dense_mx(w_f)
     b = (rng.standard_normal(N)).astype(np.float32) if bias else None
     r = pack.bf16_bits_to_f32(_bf16_bits(rng.standard_normal((M, N)).astype(np.float32))) if residual else None
@@ -154,11 +187,7 @@ def _gemm_case(M, N, K, *, bias=True, act="", residual=False, act_after_res=Fals
     d.out_fmt, d.act, d.act_after_res = out_fmt, ffi.ACT[act], int(act_after_res)
     ffi.check(ffi.lib.tfimm_hip_gemm_mx(C.byref(d), _stream()), "gemm_mx")
     torch.cuda.synchronize()
-    # accumulation: the block-scaled MFMA does not sum its 64 products in full fp32 -- measured on MI355X up to ~2e-5 *
-    # sum |a b| at K = 32 .. 3072 (fp32 MFMA chains: ~1e-7) -- so the bar is 6e-5 * sum |a b| (x the slope of the activation,
-    # <= 1.2); + the polynomial GELU of the epilogues and the fp32 roundings of the bias / residual adds
-    tol = 6e-5 * mag * 1.2 + (2e-5 if act == "gelu" else 0) + 2.0 ** -21 * (np.abs(v) + (np.abs(b) if bias else 0)
-                                                                           + (np.abs(r) if residual else 0)) + 1e-30
+    tol = mxc.gemm_tol(mag, v, act, b, r)
     if out_fmt == 2:
         return out.cpu().numpy(), osc.cpu().numpy(), v, tol
     return out.float().cpu().numpy(), None, v, tol
@@ -168,9 +197,26 @@ def _gemm_case(M, N, K, *, bias=True, act="", residual=False, act_after_res=Fals
 def test_gemm_mx_ragged_shapes(M, N, K):
     for out_fmt in (0, 1):
         got, _, ref, tol = _gemm_case(M, N, K, out_fmt=out_fmt)
-        tol = tol + (np.abs(ref) * 2.0 ** -8 if out_fmt == 0 else 0)
+        tol = mxc.bf16_tol(ref, tol) if out_fmt == 0 else tol
         bad = np.abs(got - ref) > tol
         assert not bad.any(), (out_fmt, int(bad.sum()), np.argwhere(bad)[:5], float((np.abs(got - ref) / tol).max()))
+
+
+@pytest.mark.parametrize("M,N,K", [(256, 256, 256), (257, 288, 800), (300, 96, 1536)])
+def test_gemm_mx_scales_spread_over_the_e8m0_range(M, N, K):
+    """each 32-block of A and of W with its own scale, 2^-20 .. 2^20, and zero blocks in the middle of K"""
+    got, _, ref, tol = _gemm_case(M, N, K, out_fmt=1, spread=True, seed=11)
+    bad = np.abs(got - ref) > tol
+    assert not bad.any(), (int(bad.sum()), np.argwhere(bad)[:5], float((np.abs(got - ref) / tol).max()))
+
+
+@pytest.mark.parametrize("M,N,K", [(256, 768, 768), (257, 768, 768), (3152, 3072, 768)])
+def test_gemm_mx_tile_counts(M, N, K):
+    """M = 256 / 257: one full row of tiles and one row more; 3152 x 3072 (ViT fc1 at batch 16): 156 tiles over the XCD
+    remap, more than one per XCD slot with a remainder"""
+    got, _, ref, tol = _gemm_case(M, N, K, act="gelu", residual=M != 3152, out_fmt=0, seed=5)
+    bad = np.abs(got - ref) > mxc.bf16_tol(ref, tol)
+    assert not bad.any(), (int(bad.sum()), np.argwhere(bad)[:5])
 
 
 @pytest.mark.parametrize("act", ["relu", "gelu", "swish", "sigmoid", "relu6", "tanh"])
@@ -187,24 +233,8 @@ def test_gemm_mx_epilogues(act, residual, after):
 @pytest.mark.parametrize("M,N,K,act", [(333, 384, 96, "gelu"), (96, 3072, 768, "gelu"), (64, 256, 128, "")])
 def test_gemm_mx_mxfp8_output(M, N, K, act):
     codes, scales, ref, tol = _gemm_case(M, N, K, act=act, out_fmt=2, seed=3)
-    ref32 = ref.astype(np.float32)
-    want_k = pack.mx_scale_exp(np.abs(ref32.reshape(M, N // 32, 32)).max(-1))
-    got_k = scales.astype(np.int64) - 127
-    # a block whose amax sits within the accumulation error of a scale boundary may take the neighbouring scale
-    amax = np.abs(ref.reshape(M, N // 32, 32)).max(-1)
-    tol_blk = tol.reshape(M, N // 32, 32).max(-1)
-    bnd = 448.0 * np.exp2(want_k.astype(np.float64))
-    near = (np.abs(amax - bnd) <= tol_blk) | (np.abs(amax - bnd / 2) <= tol_blk)
-    assert np.all((got_k == want_k) | near), int(((got_k != want_k) & ~near).sum())
-    s = np.exp2(got_k.astype(np.float64))[..., None]
-    y = ref.reshape(M, N // 32, 32) / s
-    gv = pack.e4m3_decode(codes).astype(np.float64).reshape(M, N // 32, 32)
-    err = np.abs(gv - y)
-    # elements: round to nearest -- half a step, plus the accumulation error of the value being rounded (so an element whose
-    # fp64 value sits on a rounding boundary may take the neighbouring code)
-    assert np.all(err <= _e4m3_step(y) * 0.5 + tol.reshape(y.shape) / s + 1e-12), float((err / _e4m3_step(y)).max())
-    exact = err <= _e4m3_step(y) * 0.5 + 1e-12
-    assert exact.mean() > 0.99, float(exact.mean())
+    fails, _ = mxc.check_mxfp8_output(codes, scales, ref, tol)
+    assert not fails, fails
 
 
 def test_gemm_mx_refuses_bad_descriptors_before_launch():
@@ -336,3 +366,121 @@ def test_fp8_plan_through_c_host(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     got = np.frombuffer(op.read_bytes(), dtype=np.float32).reshape(want.shape)
     np.testing.assert_array_equal(got, want)
+
+
+# ---- every quant_mx / gemm_mx op of real fp8 programs, teacher-forced ------------------------------------------------------
+# (quant_mx, of them with LayerNorm, gemm_mx, of them with MXFP8 output, of them whose packed weight is the named kernel's:
+# the others carry a folded LayerScale or a kernel derived on the host)
+PER_OP_COUNTS = {"vit_base_patch16_224": (36, 24, 48, 12, 48), "deit_base_distilled_patch16_224": (36, 24, 48, 12, 48),
+                 "swin_tiny_patch4_window7_224": (39, 24, 51, 12, 51), "cait_xxs24_224": (76, 48, 100, 24, 50),
+                 "convnext_tiny": (18, 18, 36, 18, 18)}
+
+
+def _read_bf16(plan, t):
+    return plan.tensor_view(t).float().cpu().numpy().reshape(plan.batch * t.rows, t.C).astype(np.float64)
+
+
+def _read_mx(plan, t):
+    """(codes [B rows, mx_ld], scale bytes [B rows, mx_ld / 32]): the scales follow the whole batch's elements"""
+    n = plan.batch * t.rows
+    slab = plan.slabs[plan.assign[t.id]]
+    e = slab[: n * t.mx_ld].cpu().numpy().reshape(n, t.mx_ld)
+    s = slab[n * t.mx_ld: n * t.mx_ld + n * (t.mx_ld // 32)].cpu().numpy().reshape(n, t.mx_ld // 32)
+    return e, s
+
+
+def _const(prog, cid):
+    return prog._dev_consts[cid].cpu().numpy()
+
+
+@pytest.mark.parametrize("name", list(PER_OP_COUNTS))
+def test_fp8_program_op_by_op(name):
+    """The fp8 program at batch 2 with every quant_mx / gemm_mx input and output kept (after lowering, so fuse_mx_outputs
+    fused as in production); each op checked against a reference built from its own read-back inputs:
+    quant_mx bit-exact (mx_checks.check_ln_quantize with LayerNorm, gamma / beta / eps from the model's weights and config),
+    gemm_mx against the fp64 product of the dequantized read-back A and the device's packed W (mx_checks.gemm_tol, bf16 or
+    MXFP8 output).  The instrumented plan's logits equal model(x) bit for bit."""
+    model = tfimm.create_model(name)
+    w = synthetic_weights(model, 2021)
+    model.set_weights(w)
+    x = mc.make_input(model.cfg, 2, 2021)
+    eps = oracle.common.LN_EPS[model.cfg.norm_layer]
+    with precision.use("fp8"):
+        want = model(x).numpy()
+        prog = model.program()
+    ops = [op for op in prog.ops if op.kind in ("quant_mx", "gemm_mx")]
+    qs = [op for op in ops if op.kind == "quant_mx"]
+    gs = [op for op in ops if op.kind == "gemm_mx"]
+    last_write = {}
+    for i, op in enumerate(prog.ops):
+        for t in ([op.output] if op.output is not None else []) + list(op.extra_outputs):
+            last_write[t] = i
+    for i, op in enumerate(prog.ops):
+        if op.kind in ("quant_mx", "gemm_mx"):
+            for t in op.inputs + [op.output]:
+                prog.tensors[t].keep = True
+                assert last_write[t] <= i, (name, op.kind, prog.tensors[t].name)   # read back = what the op saw
+    plan = prog.make_plan(2)
+    xd = torch.from_numpy(x).cuda()
+    plan.run(xd)
+    torch.cuda.synchronize()
+    got = plan.tensor_view(prog.outputs["logits"]).float().cpu().numpy().reshape(want.shape)
+    np.testing.assert_array_equal(got.view(np.uint32), want.astype(np.float32).view(np.uint32))
+
+    n_ln = n_mxo = n_packed = 0
+    worst_g, worst_o, exempt = 0.0, 0.0, 0.0
+    for op in qs:
+        xin, (q, s) = _read_bf16(plan, prog.tensors[op.inputs[0]]), _read_mx(plan, prog.tensors[op.output])
+        C = op.attrs["C"]
+        assert not q[:, C:].any() and not s[:, C // 32:].any(), (name, "padding")
+        if op.attrs["ln"]:
+            n_ln += 1
+            layer = prog.consts[op.consts["gamma"]].name.rsplit("/", 1)[0]
+            g, b = np.asarray(w[layer + "/gamma"], np.float32), np.asarray(w[layer + "/beta"], np.float32)
+            bad, ex = mxc.check_ln_quantize(q, s, xin, g, b, eps)
+            assert bad == 0, (name, layer, bad)
+            exempt = max(exempt, ex)
+        else:
+            wc, ws = pack.mx_quantize(xin.astype(np.float32))
+            nbad = int((q[:, :C] != wc).sum() + (s[:, : C // 32] != ws).sum())
+            assert nbad == 0, (name, op.cite, nbad)
+    assert exempt <= mxc.LN_EXEMPT_CAP, (name, exempt)
+    for op in gs:
+        a = op.attrs
+        K, N = a["K"], a["N"]
+        ac, asc = _read_mx(plan, prog.tensors[op.inputs[0]])
+        wc, wsc = _const(prog, op.consts["w"]), _const(prog, op.consts["w_scale"])
+        kname = prog.consts[op.consts["w"]].name[: -len(":mx")]
+        if kname in w:
+            k = np.asarray(w[kname], np.float32)
+            pw, pws = pack.pack_dense_mx(k[0, 0] if k.ndim == 4 else k)
+            n_packed += int(np.array_equal(pw, wc) and np.array_equal(pws, wsc))
+        A, Wd = pack.mx_dequantize(ac[:, :K], asc), pack.mx_dequantize(wc[:, :K], wsc)
+        v = A @ Wd.T
+        mag = np.abs(A) @ np.abs(Wd).T
+        bias = _const(prog, op.consts["bias"]).astype(np.float64) if "bias" in op.consts else None
+        if bias is not None:
+            v = v + bias
+        v = _act(v, a["act"])
+        r = _read_bf16(plan, prog.tensors[op.inputs[1]]) if a["has_residual"] else None
+        if r is not None:
+            v = v + r
+        tol = mxc.gemm_tol(mag, v, a["act"], bias, r)
+        out_t = prog.tensors[op.output]
+        if a["out_fmt"] == 2:
+            n_mxo += 1
+            oc, osc = _read_mx(plan, out_t)
+            fails, ratio = mxc.check_mxfp8_output(oc, osc, v, tol)
+            assert not fails, (name, kname, fails)
+            worst_o = max(worst_o, ratio)
+        else:
+            assert a["out_fmt"] == 0
+            o = _read_bf16(plan, out_t)
+            lim = mxc.bf16_tol(v, tol)
+            ratio = float((np.abs(o - v) / lim).max())
+            assert ratio <= 1.0, (name, kname, ratio, int((np.abs(o - v) > lim).sum()))
+            worst_g = max(worst_g, ratio)
+    assert (len(qs), n_ln, len(gs), n_mxo, n_packed) == PER_OP_COUNTS[name]
+    measured = {"ln_exempt_max": round(exempt, 6), "gemm_bf16_worst_ratio": round(worst_g, 4),
+                "gemm_mxfp8_worst_ratio": round(worst_o, 4)}
+    print("PER_OP", json.dumps({name: measured}))
