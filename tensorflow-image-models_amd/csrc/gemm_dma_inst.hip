@@ -7,7 +7,7 @@
 
 namespace tfimm_gemm {
 
-#define TFIMM_SELECT(ID, BM_, BN_, WM_, WN_)                     \
+#define TFIMM_SELECT(ID, BM_, BN_, WM_, WN_, ...)                \
   template <int I>                                               \
   struct DmaTileOf##ID {                                         \
     static constexpr int bm = BM_, bn = BN_, wm = WM_, wn = WN_; \

@@ -278,11 +278,11 @@ struct DmaTileCfg {
 }  // namespace tfimm_gemm
 
 // DMA tile shapes: id, BM, BN, WAVES_M, WAVES_N
-#define TFIMM_GEMM_DMA_TILES(X) \
-  X(0, 256, 256, 2, 4)          \
-  X(1, 256, 128, 4, 2)          \
-  X(2, 128, 128, 2, 2)          \
-  X(3, 256, 64, 4, 2)           \
-  X(4, 128, 64, 2, 2)           \
-  X(5, 128, 256, 2, 4)
+#define TFIMM_GEMM_DMA_TILES(X, ...)   \
+  X(0, 256, 256, 2, 4, __VA_ARGS__)    \
+  X(1, 256, 128, 4, 2, __VA_ARGS__)    \
+  X(2, 128, 128, 2, 2, __VA_ARGS__)    \
+  X(3, 256, 64, 4, 2, __VA_ARGS__)     \
+  X(4, 128, 64, 2, 2, __VA_ARGS__)     \
+  X(5, 128, 256, 2, 4, __VA_ARGS__)
 #define TFIMM_GEMM_DMA_NUM_TILES 6

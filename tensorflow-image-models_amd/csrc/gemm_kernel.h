@@ -397,11 +397,12 @@ struct TileCfg {
 
 }  // namespace tfimm_gemm
 
-#define TFIMM_GEMM_TILES(X) \
-  X(0, 128, 128, 2, 2)      \
-  X(1, 128, 64, 2, 2)       \
-  X(2, 64, 64, 2, 2)        \
-  X(3, 256, 128, 4, 2)      \
-  X(4, 128, 256, 2, 4)      \
-  X(5, 64, 128, 2, 2)
+// tile shapes: id, BM, BN, WAVES_M, WAVES_N; further arguments of the list are handed on to X
+#define TFIMM_GEMM_TILES(X, ...)       \
+  X(0, 128, 128, 2, 2, __VA_ARGS__)    \
+  X(1, 128, 64, 2, 2, __VA_ARGS__)     \
+  X(2, 64, 64, 2, 2, __VA_ARGS__)      \
+  X(3, 256, 128, 4, 2, __VA_ARGS__)    \
+  X(4, 128, 256, 2, 4, __VA_ARGS__)    \
+  X(5, 64, 128, 2, 2, __VA_ARGS__)
 #define TFIMM_GEMM_NUM_TILES 6

@@ -840,16 +840,22 @@ struct StreamTileCfg {
 }  // namespace tfimm_gemm
 
 // persistent tile shapes: id, BM, BN, WAVES_M, WAVES_N
-#define TFIMM_GEMM_STREAM_TILES(X) \
-  X(0, 256, 256, 2, 4)             \
-  X(1, 256, 128, 4, 2)             \
-  X(2, 128, 128, 2, 2)             \
-  X(3, 256, 64, 4, 2)              \
-  X(4, 128, 64, 2, 2)              \
-  X(5, 128, 256, 2, 4)             \
-  X(6, 256, 64, 4, 1)             \
-  X(8, 256, 32, 4, 1)
-// id 7 = the 256x256 deep-ring schedule (gemm_pipe_kernel.h), instantiated on its own; id 8 = narrow outputs
-// (N <= 32 per tile: the 24..48-channel layers of EfficientNet / MobileNet); id 9 = 256x128 with two co-resident
-// four-wave workgroups per CU (gemm_duo_kernel.h), instantiated on its own
+#define TFIMM_GEMM_STREAM_TILES(X, ...) \
+  X(0, 256, 256, 2, 4, __VA_ARGS__)     \
+  X(1, 256, 128, 4, 2, __VA_ARGS__)     \
+  X(2, 128, 128, 2, 2, __VA_ARGS__)     \
+  X(3, 256, 64, 4, 2, __VA_ARGS__)      \
+  X(4, 128, 64, 2, 2, __VA_ARGS__)      \
+  X(5, 128, 256, 2, 4, __VA_ARGS__)     \
+  X(6, 256, 64, 4, 1, __VA_ARGS__)      \
+  X(8, 256, 32, 4, 1, __VA_ARGS__)
+// id 8 = narrow outputs (N <= 32 per tile: the 24..48-channel layers of EfficientNet / MobileNet).  Two more ids of the family
+// are kernels of their own, each instantiated in its own file: id 7 = the 256x256 deep-ring schedule (gemm_pipe_kernel.h,
+// gemm_pipe_inst.hip); id 9 = 256x128 with two co-resident four-wave workgroups per CU (gemm_duo_kernel.h, gemm_duo_inst.hip).
+// Of these two rows only the id is read (the dispatcher's extern declarations and lookup): the shapes and wave counts that
+// count are the ones in the two instantiating files, which fill the records' bm / bn / threads; they are repeated for the reader
+#define TFIMM_GEMM_STREAM_OWN_TILES(X, ...) \
+  X(7, 256, 256, 2, 4, __VA_ARGS__)         \
+  X(9, 256, 128, 2, 2, __VA_ARGS__)
+#define TFIMM_GEMM_STREAM_ALL_TILES(X, ...) TFIMM_GEMM_STREAM_TILES(X, __VA_ARGS__) TFIMM_GEMM_STREAM_OWN_TILES(X, __VA_ARGS__)
 #define TFIMM_GEMM_STREAM_NUM_TILES 10

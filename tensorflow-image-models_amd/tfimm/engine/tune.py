@@ -12,6 +12,8 @@ persistent LDS-DMA tiles (ids: 256x256, 256x128, 128x128, 256x64, 128x64, 128x25
 64x64 wave tiles; 28 = 256x256 with the four-stage ring of gemm_pipe_kernel.h; 29 = 256x32 for narrow outputs;
 30 = 256x128 with two co-resident four-wave workgroups per CU, gemm_duo_kernel.h; 31 = the input-strip kernel for
 3x3 / stride 1 convolutions of 128 -> 128 channels, csrc/conv_strip.hip -- any other shape falls back to the cost model).
+Which kernel family serves which hint for which operand flavour (dense, convolution, SE gate, second operand, folded
+LayerNormalization, scalar loads) is the table at the top of csrc/gemm.hip; ``route()`` there is the code behind it.
 """
 import json
 import os
@@ -48,22 +50,24 @@ def key_of(d) -> str:
 
 
 # a layer with an SE gate on its A operand: hints 11..16 send it to the register-staged family (the LDS-DMA family has no
-# gate flavour), which scales every A element once while it stages it -- for the narrow project layers of EfficientNet that
-# beats the persistent kernels (every wave there scales the fragments it reads); its six tiles are candidates of their own
+# gate flavour: column "SE gate" of the table in csrc/gemm.hip), which scales every A element once while it stages it -- for
+# the narrow project layers of EfficientNet that beats the persistent kernels (every wave there scales the fragments it
+# reads); its six tiles are candidates of their own
 SCALE_CANDIDATES = CANDIDATES + (1, 2, 3, 4, 5, 6)
 
 
 def strip_shape(d) -> bool:
-    """The one shape the input-strip kernel (hint 31, csrc/conv_strip.hip) is built for -- what ``tfimm_hip_gemm`` checks
-    before it honours the hint: 3 x 3 / stride 1 / pad 1 convolution of 128 -> 128 channels, rows of at most 31 pixels, same
-    output size, no residual, bf16 output.  For any other shape the library answers hint 31 with its cost model, i.e. the
-    tuner would time hint 0 twice and could record 31 from noise (tests/test_tune_table.py rejects such entries)."""
+    """The one shape the input-strip kernel (hint 31, csrc/conv_strip.hip) is built for -- what ``conv_strip_applies`` in
+    csrc/gemm.hip checks before ``tfimm_hip_gemm`` honours the hint: 3 x 3 / stride 1 / pad 1 convolution of 128 -> 128
+    channels, rows of at most 31 pixels, same output size, no residual, bf16 output.  For any other shape the library
+    answers hint 31 with its cost model, i.e. the tuner would time hint 0 twice and could record 31 from noise
+    (tests/test_tune_table.py rejects such entries)."""
     pitch = getattr(d, "pix_pitch", 0) or d.Cin
     return (int(d.mode) != 0 and d.KH == 3 and d.KW == 3 and d.stride == 1 and d.Cin == 128 and d.N == 128 and 0 < d.W <= 31
             and getattr(d, "pad_t", 1) == 1 and getattr(d, "pad_l", 1) == 1 and getattr(d, "OH", d.H) == d.H
             and getattr(d, "OW", d.W) == d.W and not d.residual and not d.out_f32 and not getattr(d, "a_scale", None)
-            # ... and the rest of what tfimm_hip_gemm asks before it honours hint 31 (csrc/gemm.hip): the default stride in w, no row
-            # remap, no folded LayerNorm, K-padded weights, a pixel pitch of exactly 128 channels, 16-byte aligned output rows
+            # ... and the rest of what conv_strip_applies (csrc/gemm.hip) asks before hint 31 is honoured: the default stride in w,
+            # no row remap, no folded LayerNorm, K-padded weights, a pixel pitch of exactly 128 channels, 16-byte aligned output rows
             and getattr(d, "stride_w", 0) in (0, d.stride) and getattr(d, "remap_in", 0) == 0 and not getattr(d, "ln_stats", None)
             and getattr(d, "ldw", d.K) >= d.K and pitch == 128 and d.ldc % 8 == 0)
 

@@ -60,7 +60,7 @@ def test_strip_hint_is_a_candidate_only_for_the_strip_shape():
     assert tune.strip_shape(strip) and 31 in tune.candidates_for(strip)
     for change in (dict(W=32, OW=32), dict(Cin=64), dict(N=256), dict(stride=2), dict(KH=1, KW=1), dict(residual=0x1000),
                    dict(out_f32=1), dict(pad_t=0), dict(OH=27),
-                   #  the rest of what tfimm_hip_gemm checks before it honours the hint
+                   #  the rest of what conv_strip_applies (csrc/gemm.hip) checks before the hint is honoured
                    dict(remap_in=196, remap_out=197), dict(ln_stats=0x1000, ln_c1=0x2000), dict(ldw=1024), dict(pix_pitch=256),
                    dict(ldc=132), dict(stride_w=2)):
         d = _desc(mode=1, M=6 * 784, N=128, K=1152, lda=128, ldc=128, ldw=1152, B=6, H=28, W=28, Cin=128, KH=3, KW=3, stride=1,
