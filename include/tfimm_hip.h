@@ -63,7 +63,9 @@ enum {
 
 TFIMM_API int tfimm_hip_abi_version(void);
 TFIMM_API const char* tfimm_hip_last_error(void);
-/* Fills name[len] with e.g. "gfx950:sramecc+:xnack-"; returns CU count or <0. */
+/* Fills name[len] with e.g. "gfx950:sramecc+:xnack-" (always terminated, cut to len - 1 characters; name may be NULL, len <= 0
+ * leaves it alone); returns the CU count (> 0).  A device that does not exist or cannot be queried: returns the negated
+ * hipError_t (< 0), tfimm_hip_last_error() names the failed call and name[] is left as it was. */
 TFIMM_API int tfimm_hip_device_info(int device, char* name, int len);
 
 /* ---------------------------------------------------------------------------------------
@@ -94,7 +96,8 @@ TFIMM_API int tfimm_hip_device_info(int device, char* name, int len);
  * ------------------------------------------------------------------------------------- */
 typedef struct tfimm_gemm_desc {
   const void* a;          /* bf16 */
-  const void* wt;         /* bf16 [N][ldw], zero padded to ldw >= K, ldw % 8 == 0 */
+  const void* wt;         /* bf16 [N][ldw], zero padded to ldw >= K, ldw % 8 == 0; with a second A operand (a2) K and every one of
+                             its taps are zero padded to whole 64-wide k-tiles: ldw >= pad64(K) + taps * pad64(K2), else TFIMM_EINVAL */
   const float* bias;      /* [N] or NULL */
   const void* residual;   /* bf16 [.][ldr] or NULL */
   void* out;              /* bf16 or fp32 [.][ldc] */
@@ -143,7 +146,8 @@ typedef struct tfimm_gemm_desc {
   int32_t a2_stride, a2_H, a2_W, a2_OH, a2_OW;
   int32_t a2_window;      /* 0 / 1: the 1x1 view above.  w > 1: a w x w window of taps -- output row (b, oy, ox) reads the pixels
                              (b, oy * a2_stride + dy, ox * a2_stride + dx), dy, dx < w, as w * w further operands of K2 channels each
-                             (taps in (dy, dx) order, each padded to whole 64-wide k-tiles in wt): the average-pool shortcut of
+                             (taps in (dy, dx) order, each -- the last one too -- padded to whole 64-wide k-tiles in wt:
+                             ldw >= pad64(K) + w * w * pad64(K2)): the average-pool shortcut of
                              ResNet-D, AveragePooling2D(2, 2) + 1x1 convolution (resnet.py:295-312) = a 2x2 / stride-2 convolution whose
                              taps are the 1x1 kernel / 4.  The window must lie inside the image for every output pixel. */
 } tfimm_gemm_desc;

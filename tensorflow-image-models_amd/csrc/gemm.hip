@@ -54,8 +54,8 @@ constexpr size_t kMaxLds = 160 * 1024;
 
 // ---- environment switches: each is read once, the first time a call asks for it
 enum Env { ENV_NO_STREAM, ENV_NO_DMA, ENV_STRIP_CONV, ENV_NGROUP, ENV_DUO_DELAY_K, ENV_DUO_DELAY_0, ENV_DBG, ENV_DBG_PTR, ENV_AUTO_TILE,
-           ENV_COUNT };
-// parse: '1' = set when the first character is '1', 'i' = atoi, 'p' = strtoull of any base; unset: the value without the variable
+           ENV_LIMIT, ENV_COUNT };
+// parse: '1' = set when the first character is '1', 'i' = atoi, 'p' = strtoull of any base, 'l' = atoll; unset: the value without the variable
 struct EnvSpec { const char* name; char parse; long long unset; };
 constexpr EnvSpec kEnv[ENV_COUNT] = {
     {"TFIMM_GEMM_NO_STREAM", '1', 0},
@@ -66,11 +66,13 @@ constexpr EnvSpec kEnv[ENV_COUNT] = {
     {"TFIMM_DUO_DELAY_0", 'i', 2000},
     {"TFIMM_GEMM_DBG", 'i', 0},
     {"TFIMM_GEMM_DBG_PTR", 'p', 0},
-    {"TFIMM_GEMM_AUTO_TILE", 'i', -1}};   // probe builds only
+    {"TFIMM_GEMM_AUTO_TILE", 'i', -1},   // probe builds only
+    {"TFIMM_GEMM_LIMIT", 'l', kMaxBytes}};   // bytes: the tensor size from which chunk_rows splits a dense GEMM into row chunks (a test hook, as
+                                             // TFIMM_CHAIN_LIMIT / TFIMM_MLP_LIMIT; the buffer-descriptor bounds keep kMaxBytes)
 template <Env E> long long env() {
   static const long long v = [](const EnvSpec& s, const char* e) {
     if (!e) return s.unset;
-    return s.parse == '1' ? (long long)(e[0] == '1') : s.parse == 'i' ? (long long)atoi(e) : (long long)strtoull(e, nullptr, 0);
+    return s.parse == '1' ? (long long)(e[0] == '1') : s.parse == 'i' ? (long long)atoi(e) : s.parse == 'l' ? atoll(e) : (long long)strtoull(e, nullptr, 0);
   }(kEnv[E], getenv(kEnv[E].name));
   return v;
 }
@@ -228,9 +230,10 @@ int validate(const tfimm_gemm_desc& d) {
           (d.a2_OH - 1) * d.a2_stride + a2w > d.a2_H || (d.a2_OW - 1) * d.a2_stride + a2w > d.a2_W)
         TFIMM_FAIL(TFIMM_EINVAL, "gemm: a2 geometry %dx%d -> %dx%d at stride %d, window %d (M=%d)", d.a2_H, d.a2_W, d.a2_OH, d.a2_OW, d.a2_stride, a2w, d.M);
     }
-    // the last tap may end unpadded here; the kernels read whole k-tiles and stream_applies asks for Extents::ldw_need
-    if (d.ldw < pad64(d.K) + (int64_t)(a2w * a2w - 1) * pad64(d.K2) + d.K2)
-      TFIMM_FAIL(TFIMM_EINVAL, "gemm: ldw=%d too small for K=%d + %d taps of K2=%d (each part padded to 64)", d.ldw, d.K, a2w * a2w, d.K2);
+    // the kernels read whole 64-wide k-tiles of every part, the last tap included (Extents::ldw_need)
+    if (d.ldw < pad64(d.K) + (int64_t)(a2w * a2w) * pad64(d.K2))
+      TFIMM_FAIL(TFIMM_EINVAL, "gemm: ldw=%d too small for K=%d + %d taps of K2=%d: wt holds K and every tap padded to whole 64-wide k-tiles (ldw >= %lld)",
+                 d.ldw, d.K, a2w * a2w, d.K2, (long long)(pad64(d.K) + (int64_t)(a2w * a2w) * pad64(d.K2)));
   }
 
   if (d.mode == TFIMM_A_DENSE) {
@@ -256,12 +259,14 @@ int validate(const tfimm_gemm_desc& d) {
 
 // ---- step 2: a plain dense GEMM whose activation, output or residual exceeds 2 GiB (EfficientNet-B4's first expand layer at
 // batch 256: 9.2 M rows x 144 channels) is run as row chunks that each fit kMaxBytes, instead of leaving the LDS-DMA families.
-// Rows per chunk, 0 when the descriptor runs as it is.
+// Rows per chunk, 0 when the descriptor runs as it is.  TFIMM_GEMM_LIMIT (bytes, read once) stands in for kMaxBytes here and
+// only here, so that a test can run the chunking on a small tensor (tests/test_gpu_gemm_contract.py).
 int64_t chunk_rows(const tfimm_gemm_desc& d) {
   if (d.mode != TFIMM_A_DENSE || d.a_scale || d.a2 || d.remap_in != 0 || d.res_mod != 0) return 0;
   const int64_t row_bytes = std::max<int64_t>({(int64_t)d.lda * 2, (int64_t)d.ldc * (d.out_f32 ? 4 : 2), d.residual ? (int64_t)d.ldr * 2 : 0});
-  if (row_bytes <= 0 || (int64_t)d.M * row_bytes <= kMaxBytes || row_bytes * 512 > kMaxBytes) return 0;
-  return (kMaxBytes / row_bytes) / 256 * 256;
+  const int64_t limit = std::min<int64_t>(std::max<int64_t>(env<ENV_LIMIT>(), 1), kMaxBytes);   // TFIMM_GEMM_LIMIT lowers the threshold only
+  if (row_bytes <= 0 || (int64_t)d.M * row_bytes <= limit || row_bytes * 512 > limit) return 0;
+  return (limit / row_bytes) / 256 * 256;
 }
 
 int run_chunks(const tfimm_gemm_desc& d, int64_t chunk, void* stream) {

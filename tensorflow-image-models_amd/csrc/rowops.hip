@@ -25,7 +25,9 @@ extern "C" const char* tfimm_hip_last_error(void) { return g_err; }
 extern "C" int tfimm_hip_abi_version(void) { return TFIMM_HIP_ABI_VERSION; }
 extern "C" int tfimm_hip_device_info(int device, char* name, int len) {
   hipDeviceProp_t prop;
-  TFIMM_HIP_CHECK(hipGetDeviceProperties(&prop, device));
+  // a positive return is a CU count: a failure comes back as the NEGATED hipError_t (TFIMM_HIP_CHECK would return it as it is)
+  const hipError_t e = hipGetDeviceProperties(&prop, device);
+  if (e != hipSuccess) TFIMM_FAIL(-(int)e, "hipGetDeviceProperties(device %d) failed: %s", device, hipGetErrorString(e));
   if (name && len > 0) snprintf(name, (size_t)len, "%s", prop.gcnArchName);
   return prop.multiProcessorCount;
 }

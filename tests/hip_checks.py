@@ -1558,7 +1558,7 @@ CASES["tight_b4_dwconv_k5_336"] = _tight(lambda: _dw_case(1, 48, 48, 336, 5, 1, 
 # 3x3 / stride 1, 128 -> 128 channels on the input-strip kernel (csrc/conv_strip.hip, tile hint 31): against the oracle, and
 # bit for bit against the implicit-GEMM tile it replaces (same operand roles, same order of the K reduction)
 # ---------------------------------------------------------------------------------------------
-def _strip_conv_case(B, Hh, Ww, seed, act="relu"):
+def _strip_conv_case(B, Hh, Ww, seed, act="relu", hint=31):
     import hip_ops as H
     r = _rng(seed)
     C = 128
@@ -1570,7 +1570,7 @@ def _strip_conv_case(B, Hh, Ww, seed, act="relu"):
     y = O.activation(y, act).numpy()
     xd, wd, bd = H.dev_bf16(x), H.dev_bits(wt), H.dev_f32(bias)
     conv = dict(mode=mode, B=B, H=Hh, W=Ww, Cin=C, KH=3, KW=3, stride=1, pad_t=1, pad_l=1, OH=Hh, OW=Ww)
-    got = H.gemm(xd, wd, C, K, bias=bd, act=act, conv=conv, tile_hint=31)
+    got = H.gemm(xd, wd, C, K, bias=bd, act=act, conv=conv, tile_hint=hint)
     other = H.gemm(xd, wd, C, K, bias=bd, act=act, conv=conv, tile_hint=24)
     H.sync()
     if not torch.equal(got.view(torch.int16), other.view(torch.int16)):
@@ -1843,6 +1843,191 @@ def _act_saturation_tight_case(act, tile, seed):
 for _t in EPILOGUE_TILES:
     for _a in ("relu6", "gelu", "swish", "sigmoid", "tanh"):
         CASES[f"tight_act_saturation_{_a}_tile{_t:02d}"] = lambda a=_a, t=_t: _act_saturation_tight_case(a, t, 2000 + t)
+
+
+# --- GEMM layouts: the operand flavours classify() (csrc/gemm.hip) derives from pitches and pointer alignment -- dense_vec, res_vec,
+# res_vec16, out_vec, out_vec16, vi / ei -- each select another load or store path.  Every other GEMM case hands over fresh
+# allocations (256-byte aligned) at lda = K, ldr = ldc = N and 64-padded weights: one combination.  These cases place A, the residual
+# and the output inside larger buffers at chosen pitches and byte offsets; the pads of A and of the residual hold NaN (a kernel
+# that lets them into a sum fails), the output buffer -- pads, a guard band of rows in front and behind -- a sentinel that has to
+# survive bit for bit.
+LAYOUT_GUARD = 2                    # guard rows in front of and behind the output
+LAYOUT_SENTINEL = 0x5A5A            # bf16 bits of the output's fill (fp32: 0x5A5A5A5A)
+
+
+def _layout_out(M, N, ldc, out_off, out_f32):
+    """(flat sentinel-filled output buffer as integers of the element size, offset of out[0][0] in elements).  ``out_off`` is in bytes."""
+    es = 4 if out_f32 else 2
+    assert out_off % 2 == 0 and (not out_f32 or out_off % 4 == 0)
+    first = LAYOUT_GUARD * ldc + out_off // es
+    n = first + (M + LAYOUT_GUARD) * ldc + 8
+    fill = np.int32(0x5A5A5A5A) if out_f32 else np.int16(LAYOUT_SENTINEL)
+    return np.full(n, fill, dtype=np.int32 if out_f32 else np.int16), first
+
+
+def _layout_result(buf, first, M, N, ldc, out_f32):
+    """(the M x N result as float64, whether every element outside it still holds the sentinel)"""
+    idx = first + np.arange(M)[:, None] * ldc + np.arange(N)[None, :]
+    inside = np.zeros(buf.size, bool)
+    inside[idx.reshape(-1)] = True
+    fill = np.int32(0x5A5A5A5A) if out_f32 else np.int16(LAYOUT_SENTINEL)
+    intact = bool(np.all(buf[~inside] == fill))
+    vals = buf[idx]
+    got = vals.view(np.float32) if out_f32 else pack.bf16_bits_to_f32(vals.view(np.uint16)).reshape(M, N)
+    return got.astype(np.float64), intact
+
+
+def _layout_score(buf, first, ref, ldc, out_f32):
+    """_err of the result region, inf when a sentinel outside it changed"""
+    M, N = ref.shape
+    got, intact = _layout_result(buf, first, M, N, ldc, out_f32)
+    return _err(got, ref) if intact else float("inf")
+
+
+def _layout_strided(x, pitch, off_elems, exact_end=False):
+    """x [rows][cols] as bf16 bits in a flat NaN-filled buffer at ``pitch``, starting ``off_elems`` in; ``exact_end``: the buffer
+    ends with the last element of the last row (the bound of a buffer descriptor over it)"""
+    rows, cols = x.shape
+    n = off_elems + (rows - 1) * pitch + cols + (0 if exact_end else pitch - cols + 8)
+    flat = np.full(n, 0x7FC0, np.uint16)
+    idx = off_elems + np.arange(rows)[:, None] * pitch + np.arange(cols)[None, :]
+    flat[idx] = pack.to_bf16_bits(x).reshape(rows, cols)
+    return flat
+
+
+def _gemm_layout_case(M, K, N, *, act="gelu", residual=True, act_after_res=False, out_f32=False, tile=0, seed=0, lda=None, ldc=None,
+                      ldr=None, a_off=0, out_off=0, res_off=0, res_mod=0, ldw=None, a_exact_end=False):
+    """_gemm_case with A, the residual and the output at pitches lda / ldr / ldc and BYTE offsets a_off / res_off / out_off from
+    an aligned allocation.  ``ldw``: weights packed by hand at that pitch (K rounded up to 8: not padded to the 64 the LDS-DMA
+    families read).  The reference is _gemm_case's."""
+    import hip_ops as H
+    r = _rng(seed)
+    a = _bf(r.standard_normal((M, K)))
+    w = _bf(r.standard_normal((K, N)) / math.sqrt(K))
+    b = r.standard_normal(N).astype(np.float32)
+    nres = res_mod if res_mod else M
+    res = _bf(r.standard_normal((nres, N))) if residual else None
+    lda, ldc, ldr = lda or K, ldc or N, ldr or N
+    if ldw is None:
+        wt, _ = pack.pack_dense(w, None)
+    else:
+        assert ldw >= K and ldw % 8 == 0
+        wt = np.zeros((N, ldw), np.uint16)
+        wt[:, :K] = pack.to_bf16_bits(np.ascontiguousarray(w.T))
+    ref_t = torch.from_numpy((a.astype(np.float64) @ w.astype(np.float64) + b).astype(np.float32))
+    if not act_after_res:
+        ref_t = O.activation(ref_t, act)
+    if residual:
+        ref_t = ref_t + torch.from_numpy(res[np.arange(M) % nres])
+    if act_after_res:
+        ref_t = O.activation(ref_t, act)
+    ref = ref_t.numpy()
+    assert a_off % 2 == 0 and res_off % 2 == 0
+    ad = torch.from_numpy(_layout_strided(a, lda, a_off // 2, exact_end=a_exact_end).view(np.int16)).to(H.DEV).view(torch.bfloat16)
+    rd = None if res is None else torch.from_numpy(_layout_strided(res, ldr, res_off // 2).view(np.int16)).to(H.DEV).view(torch.bfloat16)
+    buf, first = _layout_out(M, N, ldc, out_off, out_f32)
+    od = torch.from_numpy(buf).to(H.DEV)
+    es = 4 if out_f32 else 2
+    H.gemm(ad, H.dev_bits(wt), N, K, M=M, bias=H.dev_f32(b), residual=rd, out=od, act=act, act_after_res=act_after_res, out_f32=out_f32,
+           tile_hint=tile, lda=lda, ldc=ldc, ldr=ldr, res_mod=res_mod, a_byte_offset=a_off, res_byte_offset=res_off,
+           out_byte_offset=first * es)
+    H.sync()
+    return _layout_score(od.cpu().numpy(), first, ref, ldc, out_f32), (TOL_F32 if out_f32 else TOL_BF16)
+
+
+# The tiles a layout runs on: one register-staged (3), one LDS-DMA (13), the stream tiles 21 / 28 (deep ring) / 30 (duo), as
+# EPILOGUE_TILES.  Skipped, because the table at the top of csrc/gemm.hip redirects them: hint 30 with the catch-all epilogue (the
+# duo tile has none: it runs the 256x128 stream tile), and every hint but 0 and 3 for rows that are not 16-byte aligned
+# (K_DENSE_SCALAR runs on the register-staged 64x64 tile whatever the hint; hint 13 and 21 are kept to hold that redirect itself).
+LAYOUT_VEC_TILES = (3, 13, 21, 28, 30)       # layouts that keep the vector epilogue (vi = 1)
+LAYOUT_ANY_TILES = (3, 13, 21, 28)           # layouts that send the layer to the catch-all epilogue
+LAYOUT_SHAPES = {"333x200x150": dict(M=333, K=200, N=150, act="gelu", seed=2100),
+                 "333x200x152": dict(M=333, K=200, N=152, act="gelu", seed=2101),
+                 "600x320x520_f32": dict(M=600, K=320, N=520, act="relu", act_after_res=True, out_f32=True, seed=2102)}
+# name -> (shape, tiles, layout): N below is the shape's
+LAYOUTS = {
+    # output
+    "out_ldc_n8": ("333x200x152", LAYOUT_VEC_TILES, dict(ldc=152 + 8)),                   # 16-byte stores with a pitch
+    "out_ldc_n4": ("333x200x152", LAYOUT_ANY_TILES, dict(ldc=152 + 4)),                   # out_vec without out_vec16
+    "out_off2": ("333x200x152", LAYOUT_ANY_TILES, dict(out_off=2)),                       # element stores at N % 8 == 0
+    "out_ldc_n2": ("333x200x152", (3, 13), dict(ldc=152 + 2)),
+    "out_ldc_n2_ragged": ("333x200x150", (3, 13, 21), dict(ldc=150 + 2, ldr=150 + 1)),
+    "out_f32_off8": ("600x320x520_f32", LAYOUT_ANY_TILES, dict(out_off=8)),               # fp32 rows 8-byte aligned: out_vec = 0
+    "out_f32_ldc_n4": ("600x320x520_f32", LAYOUT_ANY_TILES, dict(ldc=520 + 4)),           # fp32, out_vec = 1 with a pitch
+    "out_f32_ldc_n1": ("600x320x520_f32", (3, 13), dict(ldc=520 + 1)),
+    # residual (the output stays fully aligned: the residual alone decides the epilogue)
+    "res_ldr_n8": ("333x200x152", LAYOUT_VEC_TILES, dict(ldr=152 + 8)),                   # 16-byte reads with a pitch
+    "res_ldr_n4": ("333x200x152", LAYOUT_ANY_TILES, dict(ldr=152 + 4)),                   # res_vec only
+    "res_off8": ("333x200x152", (3, 13), dict(res_off=8)),                                # res_vec only, by the pointer
+    "res_ldr_n1": ("333x200x152", LAYOUT_ANY_TILES, dict(ldr=152 + 1)),                   # element reads
+    "res_off2": ("333x200x152", (3, 21), dict(res_off=2)),
+    "res_mod167_ldr_n8": ("333x200x152", LAYOUT_VEC_TILES, dict(res_mod=167, ldr=152 + 8)),   # res_mod >= 128 keeps the vector epilogue
+    "res_mod111_ldr_n8": ("333x200x152", (3, 13, 21), dict(res_mod=111, ldr=152 + 8)),    # res_mod < 128: catch-all
+    "res_f32_ldr_n4": ("600x320x520_f32", (3, 13, 21), dict(ldr=520 + 4)),
+    # A
+    "a_lda_k8": ("333x200x152", (0, 13, 21, 28, 30), dict(lda=200 + 8, a_exact_end=True)),    # stays on the LDS-DMA families; the last row
+    "a_lda_k8_f32": ("600x320x520_f32", (0, 13, 21), dict(lda=320 + 8, a_exact_end=True)),    # ends at the descriptor bound
+    "a_lda_k4": ("333x200x152", (0, 3, 13, 21), dict(lda=200 + 4)),                       # K_DENSE_SCALAR at K = 200
+    "a_off8": ("333x200x150", (0, 21), dict(a_off=8)),
+    "a_lda_k4_f32": ("600x320x520_f32", (0, 13), dict(lda=320 + 4)),                      # ... at K = 320
+    "a_off2_f32": ("600x320x520_f32", (0,), dict(a_off=2, lda=320 + 1)),
+    # weights not padded to the 64-wide k-tile: both LDS-DMA families refuse, hints 11-16 and 21-30 fall back to pick_tile
+    "wt_ldw200": ("333x200x152", (0, 3, 13, 24, 30), dict(ldw=200)),
+    "wt_ldw200_ragged": ("333x200x150", (0, 13, 21), dict(ldw=200)),
+    # everything at once
+    "all_pitches": ("333x200x152", LAYOUT_VEC_TILES, dict(lda=200 + 8, ldr=152 + 8, ldc=152 + 16)),
+    "all_odd": ("333x200x150", (0, 3), dict(lda=200 + 1, ldr=150 + 3, ldc=150 + 5, a_off=2, res_off=2, out_off=2, ldw=200)),
+}
+# Measured on one MI355X, worst over the family: NOT YET MEASURED -- no MI355X run of these cases has happened; the first one
+# fills in element-wise / slope / offset here, as the other families have them (the CPU model of tests/test_parity_bars.py
+# measures 0.25 / 1.5e-5 / 6.4e-6 for an honest kernel at these shapes)
+for _nm, (_shape, _tiles, _lay) in LAYOUTS.items():
+    for _t in _tiles:
+        CASES[f"tight_gemm_layout_{_nm}_tile{_t:02d}"] = _tg(
+            lambda sh=_shape, lay=_lay, t=_t: _gemm_layout_case(**LAYOUT_SHAPES[sh], **lay, tile=t))
+
+
+# --- tfimm_hip_bias_act: y = act(x + bias[c]) on bf16 rows (csrc/rowops.hip bias_act_kernel: one element per thread and grid
+# step, no vector path -- so no alignment flavour; pointer offsets of 2 bytes are run once all the same)
+def _bias_act_case(rows, C, act, bias, seed, saturate=False, off=0):
+    import hip_ops as H
+    r = _rng(seed)
+    x = r.standard_normal((rows, C)) * 3
+    if saturate:        # the pre-activations of _act_saturation_case
+        vals = np.concatenate([np.linspace(-150, 150, 301), [-3e4, -1e3, -88.8, -24.1, -16.7, 16.7, 24.1, 88.8, 1e3, 3e4]])
+        x.reshape(-1)[:] = np.resize(vals, rows * C)
+    x = _bf(x)
+    b = (r.standard_normal(C) if not saturate else np.zeros(C)).astype(np.float32) if bias else None
+    v = x.astype(np.float64) + (b.astype(np.float64) if bias else 0.0)
+    ref = O.activation(torch.from_numpy(v), act).numpy()
+    xd = torch.from_numpy(np.concatenate([np.full(off // 2, 0x7FC0, np.uint16), pack.to_bf16_bits(x).reshape(-1)]).view(np.int16)).to(H.DEV)
+    od = torch.full((off // 2 + rows * C + 8,), LAYOUT_SENTINEL, dtype=torch.int16, device=H.DEV)
+    H.bias_act(xd, None if b is None else H.dev_f32(b), act, rows=rows, c=C, out=od, x_byte_offset=off, out_byte_offset=off)
+    H.sync()
+    got = od.cpu().numpy()
+    if not (np.all(got[:off // 2] == LAYOUT_SENTINEL) and np.all(got[off // 2 + rows * C:] == LAYOUT_SENTINEL)):
+        return float("inf"), TOL_BF16
+    got = pack.bf16_bits_to_f32(got[off // 2:off // 2 + rows * C].view(np.uint16)).reshape(rows, C)
+    if saturate:
+        # element by element as _act_saturation_tight_case: a bf16 rounding of the exact value, 2e-6 absolute (GELU: its polynomial),
+        # the clamped tail; no bias bar (the slope of this set is the rounding of the two values of 3e4)
+        if not np.all(np.isfinite(got)):
+            return float("inf"), 1.0
+        tol = np.abs(ref) * 2.0 ** -8 + (GELU_POLY_ERR if act == "gelu" else 2e-6) + np.abs(v) * (2.0 ** -24 if act == "gelu" else 1e-9)
+        return float(np.max(np.abs(got - ref) / tol)), 1.0
+    return _err(got, ref), TOL_BF16
+
+
+# 1037 rows x C: (rows * C) % 256 != 0 for every C here -- a ragged last workgroup; 1037 x 1001 > 256 x 16 x 256: several grid steps
+BIAS_ACT_ACTS = ("",) + ACTS
+for _a in BIAS_ACT_ACTS:
+    for _c in (8, 100, 1001):
+        for _b in (True, False):
+            CASES[f"tight_bias_act_{_a or 'linear'}_c{_c}_{'bias' if _b else 'nobias'}"] = _tg(
+                lambda a=_a, c=_c, b=_b: _bias_act_case(1037, c, a, b, 2300 + c))
+for _a in ("swish", "sigmoid", "tanh", "gelu", "relu6"):
+    CASES[f"tight_bias_act_saturation_{_a}"] = lambda a=_a: _bias_act_case(37, 100, a, True, 2310, saturate=True)
+CASES["tight_bias_act_gelu_c100_off2"] = _tg(lambda: _bias_act_case(1037, 100, "gelu", True, 2311, off=2))
 
 
 # --- grouped / depthwise convolutions, pools, gates, head

@@ -44,12 +44,14 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def gemm(a, wt, N, K, *, M=None, bias=None, residual=None, out=None, act="", act_after_res=False,
-         out_f32=False, lda=None, ldc=None, ldr=None, res_mod=0, remap=None, conv=None, a_scale=None,
-         rows_per_image=0, tile_hint=0, out_rows=None, a_byte_offset=0, out_byte_offset=0, ln_stats=None, ln_c1=None,
-         a2=None, a2_geom=None):
-    """conv: dict(mode, B, H, W, Cin, KH, KW, stride, pad_t, pad_l, OH, OW).
-    a2: second A operand [rows2][K2] (tfimm_gemm_desc::a2); a2_geom = (stride, H, W, OH, OW[, window]) for a strided row view (window > 1: w x w taps)."""
+def gemm_desc(a, wt, N, K, *, M=None, bias=None, residual=None, out=None, act="", act_after_res=False,
+              out_f32=False, lda=None, ldc=None, ldr=None, res_mod=0, remap=None, conv=None, a_scale=None,
+              rows_per_image=0, tile_hint=0, out_rows=None, a_byte_offset=0, out_byte_offset=0, res_byte_offset=0, ln_stats=None,
+              ln_c1=None, a2=None, a2_geom=None, ldw=None):
+    """The descriptor gemm() launches, and its output tensor: (d, out).  The tensors stay the caller's to keep alive.
+    conv: dict(mode, B, H, W, Cin, KH, KW, stride, pad_t, pad_l, OH, OW).
+    a2: second A operand [rows2][K2] (tfimm_gemm_desc::a2); a2_geom = (stride, H, W, OH, OW[, window]) for a strided row view (window > 1: w x w taps).
+    *_byte_offset: added to the pointer of a / out / residual (a view into a larger allocation, or a misaligned one)."""
     d = ffi.GemmDesc()
     if conv is None:
         M = M if M is not None else a.shape[0]
@@ -64,7 +66,7 @@ def gemm(a, wt, N, K, *, M=None, bias=None, residual=None, out=None, act="", act
         d.pix_pitch = conv.get("pix_pitch", 0)
         M = conv["B"] * conv["OH"] * conv["OW"]
     d.M, d.N, d.K = M, N, K
-    d.ldw = wt.shape[1]
+    d.ldw = ldw if ldw is not None else wt.shape[1]
     rows = out_rows if out_rows is not None else M
     if out is None:
         out = torch.empty(rows, ldc or N, dtype=torch.float32 if out_f32 else torch.bfloat16, device=DEV)
@@ -75,6 +77,8 @@ def gemm(a, wt, N, K, *, M=None, bias=None, residual=None, out=None, act="", act
         d.a = ptr(a) + a_byte_offset
     if out_byte_offset:
         d.out = ptr(out) + out_byte_offset
+    if res_byte_offset:
+        d.residual = ptr(residual) + res_byte_offset
     d.ldc = ldc or N
     d.ldr = ldr or (residual.shape[-1] if residual is not None else 0)
     d.out_f32 = 1 if out_f32 else 0
@@ -98,8 +102,89 @@ def gemm(a, wt, N, K, *, M=None, bias=None, residual=None, out=None, act="", act
         from tfimm.engine import tune
         tile_hint = tune.lookup(d)
     d.tile_hint = tile_hint
+    return d, out
+
+
+def gemm_rc(d):
+    """launch a descriptor of gemm_desc(); returns (code, message) instead of raising"""
+    rc = lib.tfimm_hip_gemm(C.byref(d), stream())
+    return rc, (lib.tfimm_hip_last_error().decode() if rc else "")
+
+
+def gemm(a, wt, N, K, *, check=True, **kw):
+    """gemm_desc() launched.  check=False: returns (out, code, message) instead of raising on a non-zero code."""
+    d, out = gemm_desc(a, wt, N, K, **kw)
+    if not check:
+        return (out,) + gemm_rc(d)
     ffi.check(lib.tfimm_hip_gemm(C.byref(d), stream()), "gemm")
     return out
+
+
+def _pad64(k):
+    return -(-k // 64) * 64
+
+
+BASELINES = ("dense", "se_gate", "ln_fold", "conv", "conv_c4", "dual_dense", "dual_dense_window2", "dual_conv", "dual_conv_window2")
+
+
+def gemm_baseline(kind, N=40, seed=0, **over):
+    """One small VALID descriptor of every kind tfimm_hip_gemm takes (tests/test_gemm_contract.py breaks one field of each;
+    tests/test_gpu_gemm_contract.py launches them): (d, out, keep) -- ``keep`` holds the tensors the descriptor points into.
+    M = 72 rows = 2 images of 6 x 6; K = 72 (dense, conv 3x3 x 8 channels), 48 (C4: 3 x 4 x 4); second operand K2 = 40, as rows or as
+    2 x 2 windows of a 12 x 12 image.  Weights are zero outside their parts, every part padded to a whole 64-wide k-tile.
+    ``over``: keyword arguments of gemm_desc replacing the baseline's."""
+    r = np.random.default_rng(seed)
+    M, K, K2 = 72, 72, 40
+    geo = dict(B=2, H=6, W=6, KH=3, KW=3, stride=1, pad_t=1, pad_l=1, OH=6, OW=6)
+    kw = dict(bias=dev_f32(r.standard_normal(N)), act="relu")
+    taps = 0
+    if kind in ("dense", "se_gate", "ln_fold", "dual_dense", "dual_dense_window2"):
+        a = dev_bf16(r.standard_normal((M, K)))
+    elif kind in ("conv", "dual_conv", "dual_conv_window2"):
+        a = dev_bf16(r.standard_normal((M, 8)))
+        kw["conv"] = dict(mode=1, Cin=8, **geo)
+    elif kind == "conv_c4":
+        a, K = dev_bf16(r.standard_normal((M, 4))), 48
+        kw["conv"] = dict(mode=2, Cin=4, **geo)
+    else:
+        raise KeyError(kind)
+    if kind in ("dense", "conv"):
+        kw["residual"] = dev_bf16(r.standard_normal((M, N)))
+    if kind == "se_gate":
+        kw.update(a_scale=dev_f32(r.uniform(0.1, 1.0, (2, K))), rows_per_image=36)
+    if kind.startswith("dual"):
+        taps = 4 if kind.endswith("window2") else 1
+        kw["a2"] = dev_bf16(r.standard_normal((2 * 12 * 12 if taps == 4 else M, K2)))
+        if taps == 4:
+            kw["a2_geom"] = (2, 12, 12, 6, 6, 2)
+    w = np.zeros((N, _pad64(K) + taps * _pad64(K2)), np.float32)
+    w[:, :K] = r.standard_normal((N, K)) / np.sqrt(K)
+    for t in range(taps):
+        w[:, _pad64(K) + t * 64:_pad64(K) + t * 64 + K2] = r.standard_normal((N, K2)) / np.sqrt(K2 * taps)
+    bits = pack.to_bf16_bits(w)
+    wt = dev_bits(bits)
+    if kind == "ln_fold":
+        kw.update(ln_stats=dev_f32(np.stack([0.1 * r.standard_normal(M), r.uniform(0.5, 2.0, M)], 1)),
+                  ln_c1=dev_bits(pack.pack_ln_c1(bits, N, K)))
+    kw.update(over)
+    d, out = gemm_desc(a, wt, N, K, **kw)
+    return d, out, (a, wt, kw)
+
+
+def bias_act(x, bias, act="", rows=None, c=None, out=None, x_byte_offset=0, out_byte_offset=0):
+    rows = rows if rows is not None else x.shape[0]
+    c = c if c is not None else x.shape[-1]
+    out = out if out is not None else torch.empty(rows, c, dtype=torch.bfloat16, device=DEV)
+    ffi.check(lib.tfimm_hip_bias_act(ptr(x) + x_byte_offset, ptr(bias), ptr(out) + out_byte_offset, rows, c, ffi.ACT[act], stream()),
+              "bias_act")
+    return out
+
+
+def device_info(device=0, length=64):
+    """(CU count or negative code, architecture name) of tfimm_hip_device_info"""
+    buf = C.create_string_buffer(b"?" * (length - 1), length) if length > 0 else None
+    n = lib.tfimm_hip_device_info(device, buf, length)
+    return n, (buf.value.decode() if buf is not None else "")
 
 
 def row_stats(x, eps, rows=None, d=None, xs=None):

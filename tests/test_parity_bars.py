@@ -325,6 +325,84 @@ def test_gemm_activation_on_the_wrong_side_of_the_residual_fails():
 
 
 # ---------------------------------------------------------------------------------------------
+# GEMM layouts: the same arithmetic on operands at pitches, written into a sentinel-filled buffer (hip_checks._gemm_layout_case)
+# ---------------------------------------------------------------------------------------------
+def _gemm_layout_model(M, K, N, seed, ldr, ldc, out_off=0, defect=None):
+    """An honest kernel at pitches ldr / ldc: residual rows read at ``ldr`` from a flat NaN-padded buffer, the M x N result
+    written element by element into hip_checks' sentinel-filled output.  Defects:
+    ``res_pitch_n``   the residual read at pitch N instead of ldr (every row but the first reads its neighbours' tail and pad)
+    ``bias_shifted``  the bias added with the column offset misplaced by one 8-wide vector (column n gets bias[n + 8])
+    ``vector_store``  whole 8-wide vectors stored: the last one runs over the pad between N and ldc"""
+    r = np.random.default_rng(seed)
+    a = bf(r.standard_normal((M, K)))
+    w = bf(r.standard_normal((K, N)) / math.sqrt(K))
+    b = f32(r.standard_normal(N))
+    res = bf(r.standard_normal((M, N)))
+    flat = hc.pack.bf16_bits_to_f32(hc._layout_strided(res, ldr, 0))
+    pitch = N if defect == "res_pitch_n" else ldr
+    rk = flat[np.arange(M)[:, None] * pitch + np.arange(N)[None, :]]
+    bk = np.roll(b, -8) if defect == "bias_shifted" else b
+    acc = np.matmul(a[:, ::-1], w[::-1]).astype(np.float32) + bk
+    val = np.nan_to_num(f32(_gelu_erf(acc.astype(np.float64))) + rk, nan=0.0)            # (a NaN pad read as data: counted as 0, the mildest reading)
+    bits = hc.pack.to_bf16_bits(val).reshape(M, N).view(np.int16)
+    buf, first = hc._layout_out(M, N, ldc, out_off, False)
+    idx = first + np.arange(M)[:, None] * ldc + np.arange(N)[None, :]
+    buf[idx] = bits
+    if defect == "vector_store":
+        n8 = -(-N // 8) * 8
+        assert N < n8 <= ldc
+        buf[first + np.arange(M)[:, None] * ldc + np.arange(N, n8)[None, :]] = 0
+    ref = _gelu_erf(a.astype(np.float64) @ w.astype(np.float64) + b) + res
+    return buf, first, ref
+
+
+def _layout_score(buf, first, ref, ldc):
+    run = hc._tight(lambda: (hc._layout_score(buf, first, ref, ldc, False), 1.0), hc.STRICT, hc.BIAS_GEMM)
+    return run()[0], run.stats
+
+
+@pytest.mark.parametrize("N,ldr,ldc,off", [(152, 160, 160, 0), (152, 156, 156, 0), (150, 151, 152, 0), (152, 153, 154, 2)])
+def test_gemm_layout_honest_passes(N, ldr, ldc, off):
+    buf, first, ref = _gemm_layout_model(333, 200, N, 21, ldr, ldc, out_off=off)
+    e, st = _layout_score(buf, first, ref, ldc)
+    assert e <= 1.0 and st[0] <= 0.5, st
+
+
+def test_gemm_layout_residual_read_at_the_wrong_pitch_fails():
+    """pitch N for ldr = N + 8: row m starts 8 m elements early -- every row but the first is wrong in (nearly) every element:
+    the element-wise measure is over 50x its bar, and at least 95 % of the elements are over it"""
+    buf, first, ref = _gemm_layout_model(333, 200, 152, 21, 160, 160, defect="res_pitch_n")
+    e, st = _layout_score(buf, first, ref, 160)
+    assert e > 50.0, st
+    got, intact = hc._layout_result(buf, first, 333, 152, 160, False)
+    ulp = np.exp2(np.floor(np.log2(np.maximum(np.abs(ref), 1e-30))) - 7)
+    assert intact and np.mean(np.abs(got - ref) > 2 * ulp + 2.0 ** -14 * np.sqrt(np.mean(ref * ref))) >= 0.95
+
+
+def test_gemm_layout_bias_at_a_column_offset_misplaced_by_one_vector_fails():
+    """bias[n + 8] for bias[n]: an error of |b[n + 8] - b[n]| ~ 1 through the GELU -- over 20x the element-wise bar, at least 90 %
+    of the elements over it"""
+    buf, first, ref = _gemm_layout_model(333, 200, 152, 21, 160, 160, defect="bias_shifted")
+    e, st = _layout_score(buf, first, ref, 160)
+    assert e > 20.0, st
+    got, _ = hc._layout_result(buf, first, 333, 152, 160, False)
+    ulp = np.exp2(np.floor(np.log2(np.maximum(np.abs(ref), 1e-30))) - 7)
+    assert np.mean(np.abs(got - ref) > 2 * ulp + 2.0 ** -14 * np.sqrt(np.mean(ref * ref))) >= 0.90
+
+
+def test_gemm_layout_vector_stores_over_the_pad_fail_the_sentinel_check():
+    """N = 150, ldc = 152: values right everywhere, but two pad columns of every row overwritten"""
+    buf, first, ref = _gemm_layout_model(333, 200, 150, 21, 150, 152, defect="vector_store")
+    got, intact = hc._layout_result(buf, first, 333, 150, 152, False)
+    assert not intact and hc._err(got, ref) < 1e-2            # the values themselves are fine ...
+    e, _ = _layout_score(buf, first, ref, 152)
+    assert e == float("inf")                                   # ... the case fails all the same
+    buf, first, ref = _gemm_layout_model(333, 200, 150, 21, 150, 152)
+    buf[first - 1] = 0                                          # one element of the guard band in front
+    assert _layout_score(buf, first, ref, 152)[0] == float("inf")
+
+
+# ---------------------------------------------------------------------------------------------
 # dual-operand GEMM with a 2 x 2 window as the second operand (a2_window): four taps of the 1x1 kernel / 4
 # ---------------------------------------------------------------------------------------------
 def _dual_window_model(B, OH, OW, K1, K2, N, seed, bad_tap=None):
@@ -410,6 +488,13 @@ _TILES = [0, 1, 2, 3, 4, 5, 6, 11, 12, 13, 14, 15, 16, 21, 22, 23, 24, 25, 26, 2
 _EPI_TILES = [3, 13, 21, 28, 30]
 _SWIN = ["w7_noshift_14x14", "w7_shift3_14x14", "w7_shift3_28x14", "w7_shift3_21x35", "w7_shift3_56x56_b5", "w7_noshift_56x56_b5",
          "w7_shift3_3heads_odd", "w4_shift2_8x8_hd4", "w12_shift6_24x24"]
+_VEC, _ANY = (3, 13, 21, 28, 30), (3, 13, 21, 28)
+_LAYOUTS = [("out_ldc_n8", _VEC), ("out_ldc_n4", _ANY), ("out_off2", _ANY), ("out_ldc_n2", (3, 13)), ("out_ldc_n2_ragged", (3, 13, 21)),
+            ("out_f32_off8", _ANY), ("out_f32_ldc_n4", _ANY), ("out_f32_ldc_n1", (3, 13)), ("res_ldr_n8", _VEC), ("res_ldr_n4", _ANY),
+            ("res_off8", (3, 13)), ("res_ldr_n1", _ANY), ("res_off2", (3, 21)), ("res_mod167_ldr_n8", _VEC), ("res_mod111_ldr_n8", (3, 13, 21)),
+            ("res_f32_ldr_n4", (3, 13, 21)), ("a_lda_k8", (0, 13, 21, 28, 30)), ("a_lda_k8_f32", (0, 13, 21)), ("a_lda_k4", (0, 3, 13, 21)),
+            ("a_off8", (0, 21)), ("a_lda_k4_f32", (0, 13)), ("a_off2_f32", (0,)), ("wt_ldw200", (0, 3, 13, 24, 30)),
+            ("wt_ldw200_ragged", (0, 13, 21)), ("all_pitches", _VEC), ("all_odd", (0, 3))]
 FAMILIES = {
     "vit_attention": [f"tight_attn_197_hd{hd}" for hd in (32, 48, 64, 80, 96, 128)] + [
         "tight_attn_65_tail1", "tight_attn_64_exact", "tight_attn_256_exact", "tight_attn_577_hd64", "tight_attn_197_spike",
@@ -439,6 +524,10 @@ FAMILIES = {
         f"tight_gemm_epilogue_{a}_tile{t:02d}" for t in _EPI_TILES for a in ("relu", "relu6", "gelu", "swish", "sigmoid", "tanh",
                                                                             "swish_after_res")] + [
         f"tight_act_saturation_{a}_tile{t:02d}" for t in _EPI_TILES for a in ("relu6", "gelu", "swish", "sigmoid", "tanh")],
+    "gemm_layouts": [f"tight_gemm_layout_{n}_tile{t:02d}" for n, tiles in _LAYOUTS for t in tiles],
+    "bias_act": [f"tight_bias_act_{a}_c{c}_{b}" for a in ("linear", "relu", "relu6", "gelu", "swish", "sigmoid", "tanh")
+                 for c in (8, 100, 1001) for b in ("bias", "nobias")] + [
+        f"tight_bias_act_saturation_{a}" for a in ("swish", "sigmoid", "tanh", "gelu", "relu6")] + ["tight_bias_act_gelu_c100_off2"],
     "grouped_conv": ["tight_grouped3x3_c128_g32_56x56", "tight_grouped3x3_c256_g32_s2_odd", "tight_grouped3x3_c1024_g32_7x7",
                      "tight_grouped3x3_c96_g6_many_tiles", "tight_grouped_slice_2x64_default", "tight_grouped_slice_4x96_s2_generic_k",
                      "tight_grouped_slice_2x128_dma_family", "tight_grouped_slice_3x8_narrow"],
