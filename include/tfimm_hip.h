@@ -217,6 +217,52 @@ TFIMM_API int tfimm_hip_preprocess_input_pad(const void* in, void* out, int B, i
                                    const float* mean, const float* std, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * tfimm_hip_preprocess_resize: resize + centre crop + normalise a uint8 batch of ANY source size in one launch, written in
+ * exactly the two layouts of tfimm_hip_preprocess_input / _pad (csrc/resize.hip).  It is the evaluation transform in front
+ * of create_preprocessing (models/factory.py:128-171) that the reference leaves to the caller: every model config carries
+ * `crop_pct` and `interpolation` ("Parameters for inference", e.g. resnet.py ResNetConfig, vit.py ViTConfig) and nothing in
+ * the reference reads them.  Geometry is timm's: resize so that the crop window is input_size / crop_pct, centre crop
+ * (tfimm/models/factory.py resize_geometry); only the crop window is evaluated.
+ *
+ * Resampling is tf.image.resize(float32(img), (Rh, Rw), method, antialias=False), half-pixel centres:
+ *   bicubic  (4 taps)  Keys kernel A = -0.5 from a 1024-entry table at the rounded fractional offset, taps outside the image
+ *                      weigh 0 and the rest are renormalised; vertical pass first, then horizontal; each sum starts at 0.0
+ *                      and adds w * x in tap order, multiply and add as separate float32 operations
+ *   bilinear (2 taps)  top = tl + (tr - tl) * xf, bottom = bl + (br - bl) * xf, out = top + (bottom - top) * yf
+ * then (r / 255 - mean[c]) / std[c] in three float32 operations and one rounding to bf16 (nearest-even): the result is
+ * bit-equal to the host restatement (tfimm/models/model.py DeferredInput.numpy).  Downscaling is NOT antialiased --
+ * TensorFlow's default, a fixed 4 x 4 or 2 x 2 source pixels per output pixel; PIL-style antialiasing needs variable support.
+ *
+ * The tap tables are built on the host and passed in as device arrays; the device computes no tap arithmetic:
+ *   tfimm_hip_resize_taps  fills idx_host[n_out][taps] / w_host[n_out][taps] (taps = 2 for method 0 = bilinear, 4 for method
+ *                          1 = bicubic) for the output positions [first, first + n_out) of an axis resized from n_in to
+ *                          n_resized.  A tap outside the image has weight +0.0 and an index clamped into the image.
+ *                          Bilinear: idx = (lo, hi), w = (1 - frac, frac) -- the kernel uses w[1] as the lerp fraction.
+ *                          A plain host function: no GPU is needed or touched.
+ * The kernel clamps every index it reads from a table to the image, so a bad table cannot read out of bounds.
+ * ------------------------------------------------------------------------------------- */
+typedef struct tfimm_resize_desc {
+  const void* in;          /* uint8 [B][Hs][Ws][c_in] */
+  void* out;               /* bf16 (tfimm_hip_ref_preprocess_resize: float32) [B][H + pad_t + pad_b][W + pad_l + pad_r][c_out];
+                              channels >= c_in and the border are written as 0 */
+  const int32_t* y_idx;    /* [H][taps] source row of every tap of every output row */
+  const float* y_w;        /* [H][taps] its weight */
+  const int32_t* x_idx;    /* [W][taps] */
+  const float* x_w;        /* [W][taps] */
+  const float* mean_host;  /* HOST arrays of c_in floats (copied into the launch) */
+  const float* std_host;
+  int32_t B, Hs, Ws, c_in; /* c_in <= TFIMM_PREPROCESS_MAX_CHANNELS */
+  int32_t H, W;            /* the crop window = the model's input size */
+  int32_t c_out;           /* >= c_in; 4 (8 bytes per pixel) and 8 (16 bytes) are stored as one vector */
+  int32_t pad_t, pad_b, pad_l, pad_r;   /* the zero border of tfimm_hip_preprocess_input_pad; non-zero only with c_out == 4 */
+  int32_t taps;            /* 2 = bilinear, 4 = bicubic */
+} tfimm_resize_desc;
+
+TFIMM_API int tfimm_hip_resize_taps(int n_in, int n_resized, int first, int n_out, int method, int32_t* idx_host,
+                                    float* w_host);
+TFIMM_API int tfimm_hip_preprocess_resize(const tfimm_resize_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * tfimm_hip_layernorm: y[r][:] = (x[r][:] - mean) * rsqrt(var + eps) * gamma + beta,
  * population variance, fp32 statistics.  x row r starts at x + r*x_stride (elements),
  * y row r at y + r*y_stride.  Replaces tf.keras.layers.LayerNormalization
@@ -602,6 +648,8 @@ TFIMM_API int tfimm_hip_ref_gemm(const tfimm_gemm_desc* d, void* stream);   /* T
  * mean / std: HOST arrays of c_in floats for uint8, NULL otherwise.  out: float32 [n_pixels][c_out], channels >= c_in zero. */
 TFIMM_API int tfimm_hip_ref_cast_input(const void* in, int in_dtype, void* out, int64_t n_pixels, int c_in, int c_out,
                                        const float* mean, const float* std, void* stream);
+/* tfimm_hip_preprocess_resize with a float32 `out` (same descriptor, same arithmetic minus the rounding to bf16) */
+TFIMM_API int tfimm_hip_ref_preprocess_resize(const tfimm_resize_desc* d, void* stream);
 TFIMM_API int tfimm_hip_ref_layernorm(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int d,
                                       int64_t x_stride, int64_t y_stride, float eps, void* stream);
 TFIMM_API int tfimm_hip_ref_patch_merge_ln(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W,

@@ -112,6 +112,17 @@ class GemmMxDesc(C.Structure):
                 ("out_fmt", C.c_int32), ("act", C.c_int32), ("act_after_res", C.c_int32)]
 
 
+class ResizeDesc(C.Structure):
+    """tfimm_resize_desc: resize + centre crop + normalise of a uint8 batch (csrc/resize.hip)"""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p),
+                ("y_idx", C.c_void_p), ("y_w", C.c_void_p), ("x_idx", C.c_void_p), ("x_w", C.c_void_p),
+                ("mean_host", C.POINTER(C.c_float)), ("std_host", C.POINTER(C.c_float)),
+                ("B", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("c_in", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("c_out", C.c_int32),
+                ("pad_t", C.c_int32), ("pad_b", C.c_int32), ("pad_l", C.c_int32), ("pad_r", C.c_int32),
+                ("taps", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tfimm_hip.h
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -130,6 +141,8 @@ SYMBOLS = {
     "tfimm_hip_preprocess_input": (_i, [_vp, _vp, _i64, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
     "tfimm_hip_preprocess_input_pad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float),
                                             C.POINTER(C.c_float), _vp]),
+    "tfimm_hip_resize_taps": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "tfimm_hip_preprocess_resize": (_i, [C.POINTER(ResizeDesc), _vp]),
     "tfimm_hip_row_stats": (_i, [_vp, _vp, _i64, _i, _i64, _f, _vp]),
     "tfimm_hip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
     "tfimm_hip_attention": (_i, [C.POINTER(AttnDesc), _vp]),
@@ -159,6 +172,7 @@ SYMBOLS = {
     # float32 verification path (csrc/ref32.hip): the bf16 signatures with float tensors
     "tfimm_hip_ref_gemm": (_i, [C.POINTER(GemmDesc), _vp]),
     "tfimm_hip_ref_cast_input": (_i, [_vp, _i, _vp, _i64, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
+    "tfimm_hip_ref_preprocess_resize": (_i, [C.POINTER(ResizeDesc), _vp]),
     "tfimm_hip_ref_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
     "tfimm_hip_ref_patch_merge_ln": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "tfimm_hip_ref_copy_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -236,6 +250,22 @@ def dp_lib():
         assert L.tfimm_hip_dp_abi_version() == 1
         _dp_lib = L
     return _dp_lib
+
+
+RESIZE_METHODS = {"bilinear": 0, "bicubic": 1}
+
+
+def resize_taps(n_in: int, n_resized: int, first: int, n_out: int, method: str):
+    """tfimm_hip_resize_taps as numpy arrays: (idx int32 [n_out][taps], w float32 [n_out][taps]) of the output positions
+    [first, first + n_out) of an axis resized from ``n_in`` to ``n_resized`` -- a host function, no GPU involved."""
+    import numpy as np
+    taps = 4 if method == "bicubic" else 2
+    idx = np.zeros((n_out, taps), np.int32)
+    w = np.zeros((n_out, taps), np.float32)
+    check(lib.tfimm_hip_resize_taps(n_in, n_resized, first, n_out, RESIZE_METHODS[method],
+                                    idx.ctypes.data_as(C.POINTER(C.c_int32)), w.ctypes.data_as(C.POINTER(C.c_float))),
+          "tfimm_hip_resize_taps")
+    return idx, w
 
 
 def check(rc: int, what: str = ""):

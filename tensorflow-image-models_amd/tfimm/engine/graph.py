@@ -1138,7 +1138,11 @@ class Plan:
         self.calls: List[Tuple[Callable, tuple]] = []
         self._input_patch = None
         self._input_call = None
+        self._input_pad = (0, 0, 0, 0)          # the zero border the input step writes (cast_input op of ``_build``)
         self._stem_raw = None
+        #: (source size, norm) -> (tfimm_resize_desc, what it points to): the tap tables of a resizing input step
+        #: (launch_input), built once per source size and kept on the device
+        self._resize_tabs: Dict[tuple, tuple] = {}
         self._gemm_descs = []
         self._gemm_call_index = []
         self._tune_times = {}          # shape key -> {hint: ms} of the last isolated autotune
@@ -1185,6 +1189,7 @@ class Plan:
                 out = self.tptr(op.output)
                 H, W, cin = prog.input_shape
                 self._input_patch = (len(self.calls), out, B * H * W, a["c_in"], a["c_out"])
+                self._input_pad = tuple(a["pad"])
                 if a["pad"] != (0, 0, 0, 0):
                     pt_, pb_, pl_, pr_ = a["pad"]
                     self._input_call = (lib.tfimm_hip_cast_input_pad, (out, B, H, W, a["c_in"], pt_, pb_, pl_, pr_))
@@ -1574,6 +1579,9 @@ class Plan:
         import torch
         if self.prog.precision == "fp32":
             raise NotImplementedError("plans of the float32 verification path are not exported")
+        if self._resize_tabs:
+            raise NotImplementedError("plans run with a resize spec are not exported: tfimm_hip_plan_forward takes float32 / "
+                                      "bf16 images of the program's input size only")
         if self.device == "cpu":
             raise RuntimeError("export needs a plan built on the GPU (tile hints and occupancy are resolved there)")
         consts = self.prog._dev_consts
@@ -1736,12 +1744,27 @@ class Plan:
         """The input step of the program: convert the caller's image into the engine's padded bf16 layout
         (tfimm_hip_cast_input[_pad], or tfimm_hip_preprocess_input[_pad] for uint8 + ``norm``) -- or, when the
         program starts with the fused ResNet stem and the image is RGB float / bf16, just point that kernel at the
-        caller's image (``force_convert`` keeps the separate pass, e.g. to time it)."""
+        caller's image (``force_convert`` keeps the separate pass, e.g. to time it).  ``norm = (mean, std, (interpolation,
+        crop_pct))``: the uint8 image has a size of its own and tfimm_hip_preprocess_resize writes the same tensor, resized
+        and centre-cropped to the program's input size."""
         import torch
         c_in = self._input_patch[3]
         if (x_dev.dtype == torch.uint8) != (norm is not None):
             raise TypeError("uint8 input needs norm=(mean, std); float input must not pass it")
+        resize = None
+        if norm is not None and len(norm) > 2:
+            from ..models.factory import resize_geometry
+            H, W, _ = self.prog.input_shape
+            src = (int(x_dev.shape[1]), int(x_dev.shape[2]))
+            # source = input size and nothing cropped: the plain conversion computes the same bits (weights (0, 1, 0, 0) /
+            # fraction 0).  The source size is part of the test: crop_pct = 1 maps EVERY square source to (H, W, 0, 0)
+            if src == (H, W) and resize_geometry(src, (H, W), norm[2][1]) == (H, W, 0, 0):
+                norm = norm[:2]
+            else:
+                resize, norm = norm, norm[:2]
         if self.prog.precision == "fp32":
+            if resize is not None:
+                return self._launch_resize(x_dev, st, resize)
             mean = std = None
             if norm is not None:
                 mean = (C.c_float * c_in)(*[float(v) for v in norm[0]])
@@ -1758,6 +1781,8 @@ class Plan:
                 d.H, d.W, d.pad_t, d.pad_l = ih, iw, pad_t, pad_l
                 return 0
             d.x, d.in_dtype = padded_ptr, 0
+        if resize is not None:
+            return self._launch_resize(x_dev, st, resize)
         if norm is not None:
             mean = (C.c_float * c_in)(*[float(v) for v in norm[0]])
             std = (C.c_float * c_in)(*[float(v) for v in norm[1]])
@@ -1765,11 +1790,46 @@ class Plan:
         in_dtype = 1 if x_dev.dtype == torch.bfloat16 else 0
         return self._input_call[0](x_dev.data_ptr(), in_dtype, *self._input_call[1], st)
 
+    def _launch_resize(self, x_dev, st, norm) -> int:
+        """uint8 image of any size -> the input tensor of the program (the layout ``_input_call_u8`` writes), through
+        tfimm_hip_preprocess_resize; the float32 verification path calls the ``_ref_`` variant.  The tap tables come from the
+        library's host function, are uploaded on first use and stay cached: a recording replays them."""
+        import torch
+        from ..models.factory import resize_geometry
+        ffi = self.ffi
+        mean, std, (method, crop_pct) = norm
+        B, Hs, Ws, c_in = (int(v) for v in x_dev.shape)
+        H, W, _ = self.prog.input_shape
+        key = (Hs, Ws, norm)
+        entry = self._resize_tabs.get(key)
+        if entry is None:
+            if c_in != self._input_patch[3] or B != self.batch:
+                raise ValueError(f"resize input {tuple(x_dev.shape)} for a plan of batch {self.batch}, {self._input_patch[3]} channels")
+            Rh, Rw, top, left = resize_geometry((Hs, Ws), (H, W), crop_pct)
+            iy, wy = ffi.resize_taps(Hs, Rh, top, H, method)
+            ix, wx = ffi.resize_taps(Ws, Rw, left, W, method)
+            tabs = [torch.from_numpy(t).to(x_dev.device) for t in (iy, wy, ix, wx)]
+            d = ffi.ResizeDesc()
+            d.out = self._input_patch[1]
+            d.y_idx, d.y_w, d.x_idx, d.x_w = (t.data_ptr() for t in tabs)
+            host = ((C.c_float * c_in)(*[float(v) for v in mean]), (C.c_float * c_in)(*[float(v) for v in std]))
+            d.mean_host, d.std_host = host
+            d.B, d.Hs, d.Ws, d.c_in, d.H, d.W, d.c_out = B, Hs, Ws, c_in, H, W, self._input_patch[4]
+            d.taps = iy.shape[1]
+            if self.prog.precision != "fp32":
+                d.pad_t, d.pad_b, d.pad_l, d.pad_r = self._input_pad
+            entry = self._resize_tabs[key] = (d, tabs, host)
+        d = entry[0]
+        d.in_ = x_dev.data_ptr()
+        fn = ffi.lib.tfimm_hip_ref_preprocess_resize if self.prog.precision == "fp32" else ffi.lib.tfimm_hip_preprocess_resize
+        return fn(C.byref(d), st)
+
     def run(self, x_dev, stream_ptr: Optional[int] = None, norm=None, lo: int = 0, hi: Optional[int] = None):
         """Enqueue the whole program on the current torch stream.  ``x_dev``: contiguous cuda
         tensor (B, H, W, C) float32 or bfloat16 -- or uint8 with ``norm = (mean, std)`` (one float per
         channel): the model's preprocessing then runs inside the input conversion
-        (tfimm_hip_preprocess_input).  ``lo`` / ``hi``: only entries [lo, hi) of ``calls`` (CapturedHybrid)."""
+        (tfimm_hip_preprocess_input); ``norm = (mean, std, (interpolation, crop_pct))`` also resizes and centre-crops a
+        uint8 image of any size to the program's input size (tfimm_hip_preprocess_resize).  ``lo`` / ``hi``: only entries [lo, hi) of ``calls`` (CapturedHybrid)."""
         import torch
         ffi = self.ffi
         if stream_ptr is None:

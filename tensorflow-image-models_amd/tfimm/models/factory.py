@@ -72,8 +72,34 @@ def create_model(
     return model
 
 
+def resize_geometry(src_hw, input_size, crop_pct: float):
+    """``(Rh, Rw, top, left)``: the size a ``src_hw = (Hs, Ws)`` image is resized to and the corner of the
+    ``input_size`` crop window inside it -- timm's evaluation transform, where ``crop_pct`` comes from.
+
+    * square ``input_size`` (an int or ``(H, H)``): ``S = floor(H / crop_pct)``; the shorter source side becomes ``S``,
+      the longer one ``int(S * long / short)`` (torchvision's ``Resize(int)``);
+    * non-square ``(H, W)``: ``Rh = floor(H / crop_pct)``, ``Rw = floor(W / crop_pct)``, no aspect preservation;
+    * centre crop: ``top = round((Rh - H) / 2)``, ``left = round((Rw - W) / 2)``, halves rounding to even."""
+    import math
+    if isinstance(input_size, (int, np.integer)):
+        input_size = (int(input_size), int(input_size))
+    H, W = int(input_size[0]), int(input_size[1])
+    Hs, Ws = int(src_hw[0]), int(src_hw[1])
+    if min(H, W, Hs, Ws) <= 0 or not 0.0 < crop_pct <= 1.0:
+        raise ValueError(f"resize_geometry: bad arguments src={src_hw} input_size={input_size} crop_pct={crop_pct}")
+    if H == W:
+        S = int(math.floor(H / crop_pct))
+        if Hs <= Ws:
+            Rh, Rw = S, int(S * Ws / Hs)
+        else:
+            Rh, Rw = int(S * Hs / Ws), S
+    else:
+        Rh, Rw = int(math.floor(H / crop_pct)), int(math.floor(W / crop_pct))
+    return Rh, Rw, int(round((Rh - H) / 2)), int(round((Rw - W) / 2))     # Python's round: half to even
+
+
 def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
-                         dtype: Optional[str] = None, defer: bool = False) -> Callable:
+                         dtype: Optional[str] = None, defer: bool = False, resize: bool = False) -> Callable:
     """Function mapping [0, 255] images to model inputs: ``(img / 255 - mean) / std`` with
     mean/std tiled to ``in_channels`` (factory.py:153-169).  Works on numpy arrays and torch
     tensors, single images and batches; returns the input's array type.
@@ -81,10 +107,25 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
     ``defer=True`` (not in the reference): a **uint8** image is not converted on the host but wrapped
     in a ``DeferredInput``; ``model(pre(img))`` then evaluates the same three float32 operations inside
     the kernel that converts the input to the engine's layout -- same bits as the host path, a quarter of
-    the input bytes.  Anything that is not uint8 is preprocessed immediately as without the flag."""
+    the input bytes.  Anything that is not uint8 is preprocessed immediately as without the flag.
+
+    ``resize=True`` (not in the reference; needs ``defer=True``): the uint8 image or batch may have ANY spatial size.  The
+    ``DeferredInput`` then also carries the config's ``interpolation`` and ``crop_pct`` and the model's ``input_size``, and
+    ``model(pre(img))`` resizes, centre-crops (``resize_geometry``) and normalises in one kernel launch
+    (tfimm_hip_preprocess_resize).  Resampling is ``tf.image.resize(..., antialias=False)``: downscaling is NOT
+    antialiased (TensorFlow's default; PIL-style antialiasing is out of scope).  There is no host resize path: without
+    ``defer``, or for input that is not uint8, ``ValueError`` is raised.  ``pre(img).numpy()`` evaluates the same
+    arithmetic on the CPU, bit for bit what the device computes.  Every distinct source size makes a plan (with its
+    activation buffers) and a recording of its own on the model, as every distinct float input size does: feed batches of
+    few distinct sizes, device memory grows with their number."""
     if not is_model(model_name):
         raise ValueError(f"Unknown model: {model_name}.")
     cfg = model_config(model_name)
+    if resize and not defer:
+        raise ValueError("create_preprocessing(resize=True) needs defer=True: the resize runs on the device, inside the "
+                         "model's input conversion; there is no host resize path")
+    if resize and cfg.interpolation not in ("bicubic", "bilinear"):
+        raise ValueError(f"{model_name}: interpolation '{cfg.interpolation}' is not supported (bicubic, bilinear)")
     out_dtype = np.dtype(dtype or "float32")
     n = in_channels or cfg.in_channels
 
@@ -98,7 +139,11 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
     def _preprocess(img):
         if defer and getattr(img, "dtype", None) is not None and str(img.dtype).endswith("uint8"):
             from .model import DeferredInput
-            return DeferredInput(img, mean.astype(np.float32), std.astype(np.float32))
+            spec = (cfg.interpolation, float(cfg.crop_pct), tuple(int(v) for v in cfg.input_size)) if resize else None
+            return DeferredInput(img, mean.astype(np.float32), std.astype(np.float32), resize=spec)
+        if resize:
+            raise ValueError("create_preprocessing(resize=True) takes uint8 images only, got "
+                             f"{getattr(img, 'dtype', type(img).__name__)}: there is no host resize path")
         try:
             import torch
             if isinstance(img, torch.Tensor):

@@ -63,26 +63,68 @@ class DeferredInput:
     ``create_preprocessing(name, defer=True)`` returns for uint8 images.  ``model(x)`` consumes it directly
     -- ``(v / 255 - mean) / std`` is evaluated by the kernel that converts the input to the engine's
     bf16 layout (tfimm_hip_preprocess_input), so no float image is ever materialised.  ``numpy()`` gives
-    the float32 image the reference's preprocessing would have produced (models/factory.py:165-167)."""
+    the float32 image the reference's preprocessing would have produced (models/factory.py:165-167).  With a ``resize``
+    spec (``create_preprocessing(..., resize=True)``) the pixels may have any spatial size: resize, centre crop and
+    normalisation run in one launch (tfimm_hip_preprocess_resize) and ``numpy()`` is the same arithmetic on the CPU."""
 
-    def __init__(self, data, mean, std):
+    def __init__(self, data, mean, std, resize=None):
         self.data = data
         self.mean = tuple(float(np.float32(v)) for v in mean)
         self.std = tuple(float(np.float32(v)) for v in std)
+        #: ``create_preprocessing(..., resize=True)``: ``(interpolation, crop_pct, input_size)`` of the model config --
+        #: the pixels may have any spatial size; they are resized to ``input_size / crop_pct``, centre-cropped
+        #: (models/factory.py resize_geometry) and normalised in one launch (tfimm_hip_preprocess_resize)
+        self.resize = None if resize is None else (str(resize[0]), float(resize[1]), tuple(int(v) for v in resize[2]))
 
     @property
     def shape(self):
         return tuple(self.data.shape)
 
     def numpy(self) -> np.ndarray:
+        """The float32 model input on the CPU.  With a resize spec this is the evaluation the device performs, operation
+        for operation: the geometry of ``resize_geometry``, the tap tables of the library's host function
+        (tfimm_hip_resize_taps), the sums of ``tf.image.resize(..., antialias=False)`` -- bicubic: vertical pass, then
+        horizontal, each sum from 0.0 in tap order; bilinear: TensorFlow's compute_lerp -- then the three operations of
+        the normalisation, all in float32.  Downscaling is not antialiased."""
         d = self.data
         d = d.cpu().numpy() if hasattr(d, "cpu") else np.asarray(d)
-        x = d.astype(np.float32) / np.float32(255.0)
+        x = d.astype(np.float32)
+        if self.resize is not None:
+            x = x[None] if x.ndim == 3 else x
+            x = _resize_crop_host(x, *self.resize)
+            x = x[0] if d.ndim == 3 else x
+        x = x / np.float32(255.0)
         return (x - np.asarray(self.mean, np.float32)) / np.asarray(self.std, np.float32)
 
     def __array__(self, dtype=None, copy=None):
         a = self.numpy()
         return a.astype(dtype) if dtype is not None else a
+
+
+def _resize_crop_host(x: np.ndarray, method: str, crop_pct: float, input_size) -> np.ndarray:
+    """(B, Hs, Ws, C) float32 -> the (B, H, W, C) crop window of the resized image, in plain numpy over the library's
+    tap tables (a tap outside the image arrives as weight +0.0 at a clamped index: adding it is exact)."""
+    from ..engine import ffi
+    from .factory import resize_geometry
+    H, W = input_size
+    Hs, Ws = x.shape[1:3]
+    Rh, Rw, top, left = resize_geometry((Hs, Ws), input_size, crop_pct)
+    iy, wy = ffi.resize_taps(Hs, Rh, top, H, method)
+    ix, wx = ffi.resize_taps(Ws, Rw, left, W, method)
+    if method == "bicubic":
+        rows = np.zeros((x.shape[0], H, Ws, x.shape[3]), np.float32)
+        for t in range(4):
+            rows = rows + wy[None, :, t, None, None] * x[:, iy[:, t]]
+        out = np.zeros((x.shape[0], H, W, x.shape[3]), np.float32)
+        for t in range(4):
+            out = out + wx[None, None, :, t, None] * rows[:, :, ix[:, t]]
+        return out
+    xf, yf = wx[None, None, :, 1, None], wy[None, :, 1, None, None]
+    r0, r1 = x[:, iy[:, 0]], x[:, iy[:, 1]]
+    tl, tr, bl, br = r0[:, :, ix[:, 0]], r0[:, :, ix[:, 1]], r1[:, :, ix[:, 0]], r1[:, :, ix[:, 1]]
+    upper = tl + (tr - tl) * xf
+    lower = bl + (br - bl) * xf
+    return upper + (lower - upper) * yf
 
 
 class Model:
@@ -222,15 +264,22 @@ class Model:
         xd = self._to_device(x)
         norm = (tuple(x.mean), tuple(x.std)) if isinstance(x, DeferredInput) else None
         B, H, W, _ = xd.shape
+        src = ()
+        if norm is not None and x.resize is not None:
+            # the program is the one of the MODEL's input size; the source size only selects the tap tables, so it joins the
+            # plan / recording keys: a second source size makes a second recording instead of replaying the first one's tables
+            method, crop_pct, (H, W) = x.resize
+            norm = norm + ((method, crop_pct),)
+            src = (("src",) + tuple(xd.shape[1:3]),)
         prog = self.program(H, W, want_features)
         mb = self.micro_batch or B
         mb = min(mb, B)
         if self.branches > 1 and mb == B and B >= 2 * self.branches and prog.supports_branches():
-            return self._run_branches(prog, xd, norm, want_features)
+            return self._run_branches(prog, xd, norm, want_features, (H, W), src)
         results: Dict[str, list] = {k: [] for k in prog.outputs}
         for start in range(0, B, mb):
             nb = min(mb, B - start)
-            key = (H, W, bool(want_features), nb, precision.get())
+            key = (H, W, bool(want_features), nb, precision.get()) + src
             plan = self._plans.get(key)
             if plan is None:
                 plan = prog.make_plan(nb)
@@ -264,13 +313,13 @@ class Model:
             out[name] = v
         return out
 
-    def _run_branches(self, prog, xd, norm, want_features: bool):
+    def _run_branches(self, prog, xd, norm, want_features: bool, size, src=()):
         """The batch as ``self.branches`` slices on parallel branches of one HIP graph (engine/graph.py CapturedBranches):
         same kernels, same results, launches of different slices side by side."""
         import torch
         from ..engine.graph import CapturedBranches
-        B, H, W, _ = xd.shape
-        key = (H, W, bool(want_features), B, precision.get(), "branches", self.branches)
+        B, (H, W) = xd.shape[0], size
+        key = (H, W, bool(want_features), B, precision.get(), "branches", self.branches) + src
         plans = self._plans.get(key)
         if plans is None:
             plans = prog.make_branches(B, self.branches)
