@@ -231,7 +231,8 @@ TFIMM_API int tfimm_hip_preprocess_input_pad(const void* in, void* out, int B, i
  *   bilinear (2 taps)  top = tl + (tr - tl) * xf, bottom = bl + (br - bl) * xf, out = top + (bottom - top) * yf
  * then (r / 255 - mean[c]) / std[c] in three float32 operations and one rounding to bf16 (nearest-even): the result is
  * bit-equal to the host restatement (tfimm/models/model.py DeferredInput.numpy).  Downscaling is NOT antialiased --
- * TensorFlow's default, a fixed 4 x 4 or 2 x 2 source pixels per output pixel; PIL-style antialiasing needs variable support.
+ * TensorFlow's default, a fixed 4 x 4 or 2 x 2 source pixels per output pixel; PIL-style antialiasing is default off, see
+ * tfimm_hip_preprocess_resize_aa below.
  *
  * The tap tables are built on the host and passed in as device arrays; the device computes no tap arithmetic:
  *   tfimm_hip_resize_taps  fills idx_host[n_out][taps] / w_host[n_out][taps] (taps = 2 for method 0 = bilinear, 4 for method
@@ -261,6 +262,65 @@ typedef struct tfimm_resize_desc {
 TFIMM_API int tfimm_hip_resize_taps(int n_in, int n_resized, int first, int n_out, int method, int32_t* idx_host,
                                     float* w_host);
 TFIMM_API int tfimm_hip_preprocess_resize(const tfimm_resize_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * tfimm_hip_preprocess_resize_aa: the same launch with ANTIALIASED resampling (csrc/resize_aa.hip) -- what
+ * create_preprocessing(..., resize=True, antialias=True) runs.  Same geometry, same two output layouts (border zeros
+ * included), same normalisation and rounding as tfimm_hip_preprocess_resize.
+ *
+ * Resampling is tf.image.resize(float32(img), (Rh, Rw), method, antialias=True), the ScaleAndTranslate formulation.  No
+ * TensorFlow binary stands behind it: the rule below IS the specification, every step a float32 operation of its own.  Per
+ * axis, for the output positions o of an axis resized from n_in to n_res:
+ *   radius = 2 (bicubic) or 1 (bilinear); inv = f32(n_in) / f32(n_res); ks = max(inv, 1.0f);
+ *   T = min(2 * ceil(radius * ks) + 1, n_in)                              the span pitch
+ *   s = (f32(o) + 0.5f) * inv;  a = ceil(s - radius * ks - 0.5f), b = floor(s + radius * ks - 0.5f), both clamped to
+ *   [0, n_in - 1];  start = a, count = b - a + 1 <= T
+ *   w_i = K(|(f32(i) + 0.5f - s) / ks|) for i = a..b;  total = their sum from 0.0f in order;  if |total| >= 1000 * FLT_MIN
+ *   every w_i is multiplied by 1.0f / total;  table entries past count are +0.0
+ *   K bicubic (Keys, A = -0.5, evaluated directly): x >= 2: 0;  x >= 1: ((-0.5 x + 2.5) x - 4) x + 2;  else ((1.5 x - 2.5) x) x + 1
+ *   K bilinear: max(0, 1 - x)
+ * The vertical pass runs first into a float32 intermediate, then the horizontal pass; each sum starts at 0.0f and adds w * x
+ * in tap order, multiply and add as separate float32 operations; then (r / 255 - mean[c]) / std[c] and one rounding to bf16.
+ * An axis that is upscaled uses the same rule with ks = 1 (5 or 3 taps): as in TensorFlow, that is not bit-identical to the
+ * antialias=False launch.  An axis of scale 1 has weights (0, 0, 1, 0, 0) exactly.
+ *
+ *   tfimm_hip_resize_span_taps  returns T (or the invalid-argument code)
+ *   tfimm_hip_resize_spans      fills start_host[n_out], count_host[n_out], w_host[n_out][T] for the output positions
+ *                               [first, first + n_out); method 0 = bilinear, 1 = bicubic.  A plain host function: no GPU is
+ *                               needed or touched.  Refuses first < 0, first + n_out > n_resized, non-positive sizes and
+ *                               unknown methods with the invalid-argument code.
+ * Supported domain of the launch: y_taps, x_taps <= TFIMM_RESIZE_AA_MAX_TAPS (bicubic down to ~15 x, bilinear to ~31 x),
+ * c_in <= TFIMM_PREPROCESS_MAX_CHANNELS; anything else returns the invalid-argument code and launches nothing.  The kernel
+ * clamps every start + t to the image, so a bad table cannot read out of bounds.  One workgroup computes a tile of at most
+ * TFIMM_RESIZE_AA_TILE_ROWS x TFIMM_RESIZE_AA_TILE_COLS output pixels; at most TFIMM_RESIZE_AA_MAX_BLOCKS workgroups stride
+ * over the tiles.  The result does not depend on the tiling.
+ * ------------------------------------------------------------------------------------- */
+#define TFIMM_RESIZE_AA_MAX_TAPS 64
+#define TFIMM_RESIZE_AA_TILE_ROWS 16
+#define TFIMM_RESIZE_AA_TILE_COLS 32
+#define TFIMM_RESIZE_AA_MAX_BLOCKS 1024
+typedef struct tfimm_resize_aa_desc {
+  const void* in;          /* uint8 [B][Hs][Ws][c_in] */
+  void* out;               /* bf16 (tfimm_hip_ref_preprocess_resize_aa: float32), the layouts of tfimm_resize_desc.out */
+  const int32_t* y_start;  /* [H] first source row of the span of every output row */
+  const int32_t* y_count;  /* [H] its number of taps, <= y_taps */
+  const float* y_w;        /* [H][y_taps] the weights; entries past the count are +0.0 */
+  const int32_t* x_start;  /* [W] */
+  const int32_t* x_count;  /* [W] */
+  const float* x_w;        /* [W][x_taps] */
+  const float* mean_host;  /* HOST arrays of c_in floats (copied into the launch) */
+  const float* std_host;
+  int32_t B, Hs, Ws, c_in; /* c_in <= TFIMM_PREPROCESS_MAX_CHANNELS */
+  int32_t H, W;            /* the crop window = the model's input size */
+  int32_t c_out;           /* >= c_in; 4 (8 bytes per pixel) and 8 (16 bytes) are stored as one vector */
+  int32_t pad_t, pad_b, pad_l, pad_r;   /* the zero border; non-zero only with c_out == 4 */
+  int32_t y_taps, x_taps;  /* the span pitches T of the two axes, <= TFIMM_RESIZE_AA_MAX_TAPS */
+} tfimm_resize_aa_desc;
+
+TFIMM_API int tfimm_hip_resize_span_taps(int n_in, int n_resized, int method);
+TFIMM_API int tfimm_hip_resize_spans(int n_in, int n_resized, int first, int n_out, int method, int32_t* start_host,
+                                     int32_t* count_host, float* w_host);
+TFIMM_API int tfimm_hip_preprocess_resize_aa(const tfimm_resize_aa_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * tfimm_hip_layernorm: y[r][:] = (x[r][:] - mean) * rsqrt(var + eps) * gamma + beta,
@@ -650,6 +710,8 @@ TFIMM_API int tfimm_hip_ref_cast_input(const void* in, int in_dtype, void* out, 
                                        const float* mean, const float* std, void* stream);
 /* tfimm_hip_preprocess_resize with a float32 `out` (same descriptor, same arithmetic minus the rounding to bf16) */
 TFIMM_API int tfimm_hip_ref_preprocess_resize(const tfimm_resize_desc* d, void* stream);
+/* tfimm_hip_preprocess_resize_aa with a float32 `out` */
+TFIMM_API int tfimm_hip_ref_preprocess_resize_aa(const tfimm_resize_aa_desc* d, void* stream);
 TFIMM_API int tfimm_hip_ref_layernorm(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int d,
                                       int64_t x_stride, int64_t y_stride, float eps, void* stream);
 TFIMM_API int tfimm_hip_ref_patch_merge_ln(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W,

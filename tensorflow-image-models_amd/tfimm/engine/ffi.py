@@ -123,6 +123,18 @@ class ResizeDesc(C.Structure):
                 ("taps", C.c_int32)]
 
 
+class ResizeAADesc(C.Structure):
+    """tfimm_resize_aa_desc: the antialiased resize + centre crop + normalise of a uint8 batch (csrc/resize_aa.hip)"""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p),
+                ("y_start", C.c_void_p), ("y_count", C.c_void_p), ("y_w", C.c_void_p),
+                ("x_start", C.c_void_p), ("x_count", C.c_void_p), ("x_w", C.c_void_p),
+                ("mean_host", C.POINTER(C.c_float)), ("std_host", C.POINTER(C.c_float)),
+                ("B", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("c_in", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("c_out", C.c_int32),
+                ("pad_t", C.c_int32), ("pad_b", C.c_int32), ("pad_l", C.c_int32), ("pad_r", C.c_int32),
+                ("y_taps", C.c_int32), ("x_taps", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tfimm_hip.h
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -143,6 +155,9 @@ SYMBOLS = {
                                             C.POINTER(C.c_float), _vp]),
     "tfimm_hip_resize_taps": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "tfimm_hip_preprocess_resize": (_i, [C.POINTER(ResizeDesc), _vp]),
+    "tfimm_hip_resize_span_taps": (_i, [_i, _i, _i]),
+    "tfimm_hip_resize_spans": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "tfimm_hip_preprocess_resize_aa": (_i, [C.POINTER(ResizeAADesc), _vp]),
     "tfimm_hip_row_stats": (_i, [_vp, _vp, _i64, _i, _i64, _f, _vp]),
     "tfimm_hip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
     "tfimm_hip_attention": (_i, [C.POINTER(AttnDesc), _vp]),
@@ -173,6 +188,7 @@ SYMBOLS = {
     "tfimm_hip_ref_gemm": (_i, [C.POINTER(GemmDesc), _vp]),
     "tfimm_hip_ref_cast_input": (_i, [_vp, _i, _vp, _i64, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
     "tfimm_hip_ref_preprocess_resize": (_i, [C.POINTER(ResizeDesc), _vp]),
+    "tfimm_hip_ref_preprocess_resize_aa": (_i, [C.POINTER(ResizeAADesc), _vp]),
     "tfimm_hip_ref_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
     "tfimm_hip_ref_patch_merge_ln": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "tfimm_hip_ref_copy_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -266,6 +282,50 @@ def resize_taps(n_in: int, n_resized: int, first: int, n_out: int, method: str):
                                     idx.ctypes.data_as(C.POINTER(C.c_int32)), w.ctypes.data_as(C.POINTER(C.c_float))),
           "tfimm_hip_resize_taps")
     return idx, w
+
+
+# include/tfimm_hip.h: the domain and the tiling of tfimm_hip_preprocess_resize_aa
+RESIZE_AA_MAX_TAPS = 64
+RESIZE_AA_TILE_ROWS, RESIZE_AA_TILE_COLS, RESIZE_AA_MAX_BLOCKS = 16, 32, 1024
+
+
+def resize_span_taps(n_in: int, n_resized: int, method: str) -> int:
+    """tfimm_hip_resize_span_taps: the span pitch T of an axis resized from ``n_in`` to ``n_resized`` with antialiasing"""
+    t = lib.tfimm_hip_resize_span_taps(n_in, n_resized, RESIZE_METHODS[method])
+    if t <= 0:
+        check(t or -1, "tfimm_hip_resize_span_taps")
+    return t
+
+
+def resize_spans(n_in: int, n_resized: int, first: int, n_out: int, method: str):
+    """tfimm_hip_resize_spans as numpy arrays: (start int32 [n_out], count int32 [n_out], w float32 [n_out][T]) of the output
+    positions [first, first + n_out) of an axis resized from ``n_in`` to ``n_resized`` with antialiasing; entries of ``w`` past
+    ``count`` are +0.0 -- a host function, no GPU involved."""
+    import numpy as np
+    if n_out <= 0:
+        raise HipError(f"tfimm_hip_resize_spans: n_out={n_out}")
+    T = resize_span_taps(n_in, n_resized, method)
+    start, count = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32)
+    w = np.zeros((n_out, T), np.float32)
+    check(lib.tfimm_hip_resize_spans(n_in, n_resized, first, n_out, RESIZE_METHODS[method],
+                                     start.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     w.ctypes.data_as(C.POINTER(C.c_float))),
+          "tfimm_hip_resize_spans")
+    return start, count, w
+
+
+def resize_aa_tables(src_hw, geometry, size, method: str):
+    """The span tables of tfimm_hip_preprocess_resize_aa for a ``src_hw`` image resized to ``geometry = (Rh, Rw, top, left)``
+    and cropped to ``size``: ``((y_start, y_count, y_w), (x_start, x_count, x_w))``.  ``ValueError`` when an axis shrinks
+    further than the launch supports -- checked here, on the host, before anything is uploaded."""
+    (Hs, Ws), (Rh, Rw, top, left), (H, W) = src_hw, geometry, size
+    for axis, n_in, n_res in (("height", Hs, Rh), ("width", Ws, Rw)):
+        T = resize_span_taps(n_in, n_res, method)
+        if T > RESIZE_AA_MAX_TAPS:
+            raise ValueError(f"antialiased {method} resize of the {axis} {n_in} -> {n_res} needs {T} taps per output pixel, "
+                             f"more than TFIMM_RESIZE_AA_MAX_TAPS = {RESIZE_AA_MAX_TAPS}: the source is too large for the "
+                             "device resize, shrink it on the host first")
+    return resize_spans(Hs, Rh, top, H, method), resize_spans(Ws, Rw, left, W, method)
 
 
 def check(rc: int, what: str = ""):

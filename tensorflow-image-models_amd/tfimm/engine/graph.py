@@ -1140,7 +1140,8 @@ class Plan:
         self._input_call = None
         self._input_pad = (0, 0, 0, 0)          # the zero border the input step writes (cast_input op of ``_build``)
         self._stem_raw = None
-        #: (source size, norm) -> (tfimm_resize_desc, what it points to): the tap tables of a resizing input step
+        #: (source size, norm) -> (tfimm_resize_desc or tfimm_resize_aa_desc, what it points to): the tap / span tables of a
+        #: resizing input step; ``norm`` carries the antialias flag
         #: (launch_input), built once per source size and kept on the device
         self._resize_tabs: Dict[tuple, tuple] = {}
         self._gemm_descs = []
@@ -1746,7 +1747,8 @@ class Plan:
         program starts with the fused ResNet stem and the image is RGB float / bf16, just point that kernel at the
         caller's image (``force_convert`` keeps the separate pass, e.g. to time it).  ``norm = (mean, std, (interpolation,
         crop_pct))``: the uint8 image has a size of its own and tfimm_hip_preprocess_resize writes the same tensor, resized
-        and centre-cropped to the program's input size."""
+        and centre-cropped to the program's input size; ``(interpolation, crop_pct, True)`` does so with antialiasing
+        (tfimm_hip_preprocess_resize_aa)."""
         import torch
         c_in = self._input_patch[3]
         if (x_dev.dtype == torch.uint8) != (norm is not None):
@@ -1757,7 +1759,7 @@ class Plan:
             H, W, _ = self.prog.input_shape
             src = (int(x_dev.shape[1]), int(x_dev.shape[2]))
             # source = input size and nothing cropped: the plain conversion computes the same bits (weights (0, 1, 0, 0) /
-            # fraction 0).  The source size is part of the test: crop_pct = 1 maps EVERY square source to (H, W, 0, 0)
+            # fraction 0; antialiased: (0, 0, 1, 0, 0)).  The source size is part of the test: crop_pct = 1 maps EVERY square source to (H, W, 0, 0)
             if src == (H, W) and resize_geometry(src, (H, W), norm[2][1]) == (H, W, 0, 0):
                 norm = norm[:2]
             else:
@@ -1793,11 +1795,13 @@ class Plan:
     def _launch_resize(self, x_dev, st, norm) -> int:
         """uint8 image of any size -> the input tensor of the program (the layout ``_input_call_u8`` writes), through
         tfimm_hip_preprocess_resize; the float32 verification path calls the ``_ref_`` variant.  The tap tables come from the
-        library's host function, are uploaded on first use and stay cached: a recording replays them."""
+        library's host function, are uploaded on first use and stay cached: a recording replays them.  An antialiased spec
+        (``norm[2]`` ends in ``True``) takes the span tables and tfimm_hip_preprocess_resize_aa instead."""
         import torch
         from ..models.factory import resize_geometry
         ffi = self.ffi
-        mean, std, (method, crop_pct) = norm
+        mean, std, (method, crop_pct, *aa) = norm
+        aa = bool(aa and aa[0])
         B, Hs, Ws, c_in = (int(v) for v in x_dev.shape)
         H, W, _ = self.prog.input_shape
         key = (Hs, Ws, norm)
@@ -1806,30 +1810,39 @@ class Plan:
             if c_in != self._input_patch[3] or B != self.batch:
                 raise ValueError(f"resize input {tuple(x_dev.shape)} for a plan of batch {self.batch}, {self._input_patch[3]} channels")
             Rh, Rw, top, left = resize_geometry((Hs, Ws), (H, W), crop_pct)
-            iy, wy = ffi.resize_taps(Hs, Rh, top, H, method)
-            ix, wx = ffi.resize_taps(Ws, Rw, left, W, method)
-            tabs = [torch.from_numpy(t).to(x_dev.device) for t in (iy, wy, ix, wx)]
-            d = ffi.ResizeDesc()
+            if aa:
+                # ValueError before anything is uploaded when an axis shrinks beyond TFIMM_RESIZE_AA_MAX_TAPS
+                ty, tx = ffi.resize_aa_tables((Hs, Ws), (Rh, Rw, top, left), (H, W), method)
+                tabs = [torch.from_numpy(t).to(x_dev.device) for t in ty + tx]
+                d = ffi.ResizeAADesc()
+                d.y_start, d.y_count, d.y_w, d.x_start, d.x_count, d.x_w = (t.data_ptr() for t in tabs)
+                d.y_taps, d.x_taps = ty[2].shape[1], tx[2].shape[1]
+            else:
+                iy, wy = ffi.resize_taps(Hs, Rh, top, H, method)
+                ix, wx = ffi.resize_taps(Ws, Rw, left, W, method)
+                tabs = [torch.from_numpy(t).to(x_dev.device) for t in (iy, wy, ix, wx)]
+                d = ffi.ResizeDesc()
+                d.y_idx, d.y_w, d.x_idx, d.x_w = (t.data_ptr() for t in tabs)
+                d.taps = iy.shape[1]
             d.out = self._input_patch[1]
-            d.y_idx, d.y_w, d.x_idx, d.x_w = (t.data_ptr() for t in tabs)
             host = ((C.c_float * c_in)(*[float(v) for v in mean]), (C.c_float * c_in)(*[float(v) for v in std]))
             d.mean_host, d.std_host = host
             d.B, d.Hs, d.Ws, d.c_in, d.H, d.W, d.c_out = B, Hs, Ws, c_in, H, W, self._input_patch[4]
-            d.taps = iy.shape[1]
             if self.prog.precision != "fp32":
                 d.pad_t, d.pad_b, d.pad_l, d.pad_r = self._input_pad
             entry = self._resize_tabs[key] = (d, tabs, host)
         d = entry[0]
         d.in_ = x_dev.data_ptr()
-        fn = ffi.lib.tfimm_hip_ref_preprocess_resize if self.prog.precision == "fp32" else ffi.lib.tfimm_hip_preprocess_resize
-        return fn(C.byref(d), st)
+        fn = "tfimm_hip_ref_preprocess_resize" if self.prog.precision == "fp32" else "tfimm_hip_preprocess_resize"
+        return getattr(ffi.lib, fn + ("_aa" if aa else ""))(C.byref(d), st)
 
     def run(self, x_dev, stream_ptr: Optional[int] = None, norm=None, lo: int = 0, hi: Optional[int] = None):
         """Enqueue the whole program on the current torch stream.  ``x_dev``: contiguous cuda
         tensor (B, H, W, C) float32 or bfloat16 -- or uint8 with ``norm = (mean, std)`` (one float per
         channel): the model's preprocessing then runs inside the input conversion
         (tfimm_hip_preprocess_input); ``norm = (mean, std, (interpolation, crop_pct))`` also resizes and centre-crops a
-        uint8 image of any size to the program's input size (tfimm_hip_preprocess_resize).  ``lo`` / ``hi``: only entries [lo, hi) of ``calls`` (CapturedHybrid)."""
+        uint8 image of any size to the program's input size (tfimm_hip_preprocess_resize; ``(interpolation, crop_pct, True)``: antialiased,
+        tfimm_hip_preprocess_resize_aa).  ``lo`` / ``hi``: only entries [lo, hi) of ``calls`` (CapturedHybrid)."""
         import torch
         ffi = self.ffi
         if stream_ptr is None:

@@ -99,7 +99,8 @@ def resize_geometry(src_hw, input_size, crop_pct: float):
 
 
 def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
-                         dtype: Optional[str] = None, defer: bool = False, resize: bool = False) -> Callable:
+                         dtype: Optional[str] = None, defer: bool = False, resize: bool = False,
+                         antialias: bool = False) -> Callable:
     """Function mapping [0, 255] images to model inputs: ``(img / 255 - mean) / std`` with
     mean/std tiled to ``in_channels`` (factory.py:153-169).  Works on numpy arrays and torch
     tensors, single images and batches; returns the input's array type.
@@ -113,17 +114,27 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
     ``DeferredInput`` then also carries the config's ``interpolation`` and ``crop_pct`` and the model's ``input_size``, and
     ``model(pre(img))`` resizes, centre-crops (``resize_geometry``) and normalises in one kernel launch
     (tfimm_hip_preprocess_resize).  Resampling is ``tf.image.resize(..., antialias=False)``: downscaling is NOT
-    antialiased (TensorFlow's default; PIL-style antialiasing is out of scope).  There is no host resize path: without
+    antialiased (TensorFlow's default; antialiasing is default off, see ``antialias`` below).  There is no host resize path: without
     ``defer``, or for input that is not uint8, ``ValueError`` is raised.  ``pre(img).numpy()`` evaluates the same
     arithmetic on the CPU, bit for bit what the device computes.  Every distinct source size makes a plan (with its
     activation buffers) and a recording of its own on the model, as every distinct float input size does: feed batches of
-    few distinct sizes, device memory grows with their number."""
+    few distinct sizes, device memory grows with their number.
+
+    ``antialias=True`` (needs ``resize=True``): resampling is ``tf.image.resize(..., antialias=True)`` -- every output pixel
+    sums a span of source pixels that grows with the scale, as PIL's resize does and as the pretrained weights were
+    evaluated; without it a 480 x 640 frame going to 224 skips almost half of its source pixels.  One launch as before
+    (tfimm_hip_preprocess_resize_aa), ``pre(img).numpy()`` again the same arithmetic bit for bit.  An axis
+    may shrink to about 1/15 (bicubic) or 1/31 (bilinear) of its size; beyond that ``model(pre(img))`` raises
+    ``ValueError`` (TFIMM_RESIZE_AA_MAX_TAPS).  Antialiased and plain input of the same source size use separate plans and
+    recordings."""
     if not is_model(model_name):
         raise ValueError(f"Unknown model: {model_name}.")
     cfg = model_config(model_name)
     if resize and not defer:
         raise ValueError("create_preprocessing(resize=True) needs defer=True: the resize runs on the device, inside the "
                          "model's input conversion; there is no host resize path")
+    if antialias and not resize:
+        raise ValueError("create_preprocessing(antialias=True) needs resize=True: antialiasing is part of the device resize")
     if resize and cfg.interpolation not in ("bicubic", "bilinear"):
         raise ValueError(f"{model_name}: interpolation '{cfg.interpolation}' is not supported (bicubic, bilinear)")
     out_dtype = np.dtype(dtype or "float32")
@@ -140,6 +151,8 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
         if defer and getattr(img, "dtype", None) is not None and str(img.dtype).endswith("uint8"):
             from .model import DeferredInput
             spec = (cfg.interpolation, float(cfg.crop_pct), tuple(int(v) for v in cfg.input_size)) if resize else None
+            if antialias:
+                spec += (True,)
             return DeferredInput(img, mean.astype(np.float32), std.astype(np.float32), resize=spec)
         if resize:
             raise ValueError("create_preprocessing(resize=True) takes uint8 images only, got "

@@ -65,7 +65,8 @@ class DeferredInput:
     bf16 layout (tfimm_hip_preprocess_input), so no float image is ever materialised.  ``numpy()`` gives
     the float32 image the reference's preprocessing would have produced (models/factory.py:165-167).  With a ``resize``
     spec (``create_preprocessing(..., resize=True)``) the pixels may have any spatial size: resize, centre crop and
-    normalisation run in one launch (tfimm_hip_preprocess_resize) and ``numpy()`` is the same arithmetic on the CPU."""
+    normalisation run in one launch (tfimm_hip_preprocess_resize; with ``antialias=True`` tfimm_hip_preprocess_resize_aa) and
+    ``numpy()`` is the same arithmetic on the CPU."""
 
     def __init__(self, data, mean, std, resize=None):
         self.data = data
@@ -74,7 +75,10 @@ class DeferredInput:
         #: ``create_preprocessing(..., resize=True)``: ``(interpolation, crop_pct, input_size)`` of the model config --
         #: the pixels may have any spatial size; they are resized to ``input_size / crop_pct``, centre-cropped
         #: (models/factory.py resize_geometry) and normalised in one launch (tfimm_hip_preprocess_resize)
+        #: ``antialias=True`` appends ``True`` (tfimm_hip_preprocess_resize_aa); without it the spec has three entries
         self.resize = None if resize is None else (str(resize[0]), float(resize[1]), tuple(int(v) for v in resize[2]))
+        if resize is not None and len(resize) > 3 and resize[3]:
+            self.resize += (True,)
 
     @property
     def shape(self):
@@ -85,7 +89,9 @@ class DeferredInput:
         for operation: the geometry of ``resize_geometry``, the tap tables of the library's host function
         (tfimm_hip_resize_taps), the sums of ``tf.image.resize(..., antialias=False)`` -- bicubic: vertical pass, then
         horizontal, each sum from 0.0 in tap order; bilinear: TensorFlow's compute_lerp -- then the three operations of
-        the normalisation, all in float32.  Downscaling is not antialiased."""
+        the normalisation, all in float32.  Downscaling is not antialiased unless the spec says so: then the sums run
+        over the span tables of tfimm_hip_resize_spans (``tf.image.resize(..., antialias=True)``), vertical pass first,
+        each sum from 0.0 in tap order, for both methods."""
         d = self.data
         d = d.cpu().numpy() if hasattr(d, "cpu") else np.asarray(d)
         x = d.astype(np.float32)
@@ -101,7 +107,7 @@ class DeferredInput:
         return a.astype(dtype) if dtype is not None else a
 
 
-def _resize_crop_host(x: np.ndarray, method: str, crop_pct: float, input_size) -> np.ndarray:
+def _resize_crop_host(x: np.ndarray, method: str, crop_pct: float, input_size, antialias: bool = False) -> np.ndarray:
     """(B, Hs, Ws, C) float32 -> the (B, H, W, C) crop window of the resized image, in plain numpy over the library's
     tap tables (a tap outside the image arrives as weight +0.0 at a clamped index: adding it is exact)."""
     from ..engine import ffi
@@ -109,6 +115,17 @@ def _resize_crop_host(x: np.ndarray, method: str, crop_pct: float, input_size) -
     H, W = input_size
     Hs, Ws = x.shape[1:3]
     Rh, Rw, top, left = resize_geometry((Hs, Ws), input_size, crop_pct)
+    if antialias:
+        # span tables: entries past a span's count weigh +0.0 (at an index clamped into the image), so every row and
+        # column sums over the whole pitch
+        (ys, _, wy), (xs, _, wx) = ffi.resize_spans(Hs, Rh, top, H, method), ffi.resize_spans(Ws, Rw, left, W, method)
+        rows = np.zeros((x.shape[0], H, Ws, x.shape[3]), np.float32)
+        for t in range(wy.shape[1]):
+            rows = rows + wy[None, :, t, None, None] * x[:, np.minimum(ys + t, Hs - 1)]
+        out = np.zeros((x.shape[0], H, W, x.shape[3]), np.float32)
+        for t in range(wx.shape[1]):
+            out = out + wx[None, None, :, t, None] * rows[:, :, np.minimum(xs + t, Ws - 1)]
+        return out
     iy, wy = ffi.resize_taps(Hs, Rh, top, H, method)
     ix, wx = ffi.resize_taps(Ws, Rw, left, W, method)
     if method == "bicubic":
@@ -268,9 +285,11 @@ class Model:
         if norm is not None and x.resize is not None:
             # the program is the one of the MODEL's input size; the source size only selects the tap tables, so it joins the
             # plan / recording keys: a second source size makes a second recording instead of replaying the first one's tables
-            method, crop_pct, (H, W) = x.resize
-            norm = norm + ((method, crop_pct),)
-            src = (("src",) + tuple(xd.shape[1:3]),)
+            method, crop_pct, (H, W) = x.resize[:3]
+            # antialiased resampling is another input step over other tables: a plan and a recording of its own
+            aa = len(x.resize) > 3
+            norm = norm + ((method, crop_pct) + ((True,) if aa else ()),)
+            src = (("src",) + tuple(xd.shape[1:3]) + (("antialias",) if aa else ()),)
         prog = self.program(H, W, want_features)
         mb = self.micro_batch or B
         mb = min(mb, B)
