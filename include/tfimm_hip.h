@@ -323,6 +323,108 @@ TFIMM_API int tfimm_hip_resize_spans(int n_in, int n_resized, int first, int n_o
 TFIMM_API int tfimm_hip_preprocess_resize_aa(const tfimm_resize_aa_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * tfimm_hip_preprocess_resize_batch / _batch_aa: the two launches above for a batch whose images each have a SIZE OF THEIR
+ * OWN (csrc/resize_batch.hip) -- what create_preprocessing(..., resize=True) runs for a LIST of images.
+ * For image b they compute exactly what tfimm_hip_preprocess_resize[_aa] computes for that image alone at B = 1: the same
+ * tables, the same float32 operations in the same order, the same normalisation, one rounding to bf16, the same two output
+ * layouts (border zeros written by the kernel).
+ *
+ * Everything that varies with the sources lives in DEVICE memory; the descriptor holds pointers, the output geometry and
+ * capacities only, and the grid and the LDS size are functions of those scalars.  A recording of the launch (hipGraph) is
+ * therefore valid for any later contents of the buffers: one recording serves every mix of sizes.
+ *   in     one uint8 arena of in_bytes bytes; image b is packed [Hs_b][Ws_b][c_in] at byte offset recs[b].in_offset --
+ *          any offset, no alignment (source loads are byte loads)
+ *   recs   B records tfimm_resize_batch_rec, one per image
+ *   plain  idx / w arenas of B * (H + W) * taps entries: the tables of tfimm_hip_resize_taps, image b's rows at element
+ *          recs[b].y_tab, its columns at recs[b].x_tab
+ *   aa     start / count arenas of B * (H + W) entries (image b's rows at recs[b].y_tab, its columns at recs[b].x_tab) and
+ *          a weight arena of w_floats floats: image b's row weights [H][y_taps] at float recs[b].y_w, its column weights
+ *          [W][x_taps] at recs[b].x_w -- every image at its own pitches (the tables of tfimm_hip_resize_spans)
+ * tfimm_hip_resize_batch_tables below builds records and arenas on the host.  The kernels trust none of it: every table
+ * index is clamped into its image, every source byte offset into [0, in_bytes), every table offset into its arena, every
+ * pitch into [1, taps_cap], every tile shape into the LDS allocation; all global offsets are 64-bit.  A stale or bad record
+ * gives wrong pixels, never an access out of bounds.
+ *
+ * Plain launch: one thread per output pixel, at most 4096 workgroups stride over B * HP * WP pixels.  Antialiased launch:
+ * workgroups (at most TFIMM_RESIZE_AA_MAX_BLOCKS) stride over the tiles of all images -- image b owns the tile indices
+ * [tile0, tile0 + n_tiles) of its record, tile_rows x TFIMM_RESIZE_AA_TILE_COLS output pixels each, found by a binary
+ * search over the records -- with lds_bytes of dynamic LDS (0 = the 64 KiB budget of the uniform launch; a caller that knows
+ * its largest tile, tfimm_resize_batch_sizes.lds_floats, may pass less to raise occupancy: the size still depends on no
+ * single batch as long as the caller keeps it a capacity).
+ * Refused with the invalid-argument code, nothing launched: null pointers, non-positive sizes, c_in >
+ * TFIMM_PREPROCESS_MAX_CHANNELS, c_out < c_in, a padded layout with c_out != 4, std == 0, taps not 2 or 4, taps_cap >
+ * TFIMM_RESIZE_AA_MAX_TAPS, lds_bytes > 64 KiB.
+ * ------------------------------------------------------------------------------------- */
+typedef struct tfimm_resize_batch_rec {
+  int64_t in_offset;       /* byte offset of the image in the pixel arena */
+  int32_t Hs, Ws;          /* its size */
+  int32_t y_tab, x_tab;    /* element offsets of its row / column tables: plain, into idx and w (taps entries per position);
+                              aa, into start and count (one entry per position) */
+  int32_t y_w, x_w;        /* aa: float offsets of its row / column weights in the weight arena (plain: = y_tab, x_tab) */
+  int32_t y_taps, x_taps;  /* aa: its span pitches (plain: taps) */
+  int32_t tile_rows;       /* aa: output rows of a tile of this image (the rule of the uniform launch; plain: 0) */
+  int32_t cols_max;        /* aa: source columns an LDS row of its tiles holds */
+  int32_t tile0, n_tiles;  /* aa: its first tile in the launch's numbering, and how many it has */
+} tfimm_resize_batch_rec;
+
+typedef struct tfimm_resize_batch_desc {
+  const void* in;          /* uint8 arena, in_bytes bytes */
+  const tfimm_resize_batch_rec* recs;   /* DEVICE [B] */
+  void* out;               /* bf16 (tfimm_hip_ref_preprocess_resize_batch: float32), the layouts of tfimm_resize_desc.out */
+  const int32_t* idx;      /* DEVICE [B * (H + W) * taps] */
+  const float* w;          /* DEVICE [B * (H + W) * taps] */
+  const float* mean_host;  /* HOST arrays of c_in floats (copied into the launch) */
+  const float* std_host;
+  int64_t in_bytes;
+  int32_t B, c_in, H, W, c_out;
+  int32_t pad_t, pad_b, pad_l, pad_r;
+  int32_t taps;            /* 2 = bilinear, 4 = bicubic */
+} tfimm_resize_batch_desc;
+
+typedef struct tfimm_resize_batch_aa_desc {
+  const void* in;          /* uint8 arena, in_bytes bytes */
+  const tfimm_resize_batch_rec* recs;   /* DEVICE [B] */
+  void* out;
+  const int32_t* start;    /* DEVICE [B * (H + W)] */
+  const int32_t* count;    /* DEVICE [B * (H + W)] */
+  const float* w;          /* DEVICE [w_floats] */
+  const float* mean_host;
+  const float* std_host;
+  int64_t in_bytes;
+  int64_t w_floats;        /* capacity of the weight arena */
+  int32_t B, c_in, H, W, c_out;
+  int32_t pad_t, pad_b, pad_l, pad_r;
+  int32_t taps_cap;        /* the largest pitch a record may name, <= TFIMM_RESIZE_AA_MAX_TAPS */
+  int32_t lds_bytes;       /* dynamic LDS of a workgroup, a multiple of 4 and <= 64 KiB; 0 = 64 KiB */
+} tfimm_resize_batch_aa_desc;
+
+/* What a mixed batch needs, reported by tfimm_hip_resize_batch_tables */
+typedef struct tfimm_resize_batch_sizes {
+  int64_t in_bytes;        /* the images packed back to back in list order: the sum of Hs * Ws * c_in */
+  int64_t tab_elems;       /* entries of idx and of w (plain) or of start and of count (aa) */
+  int64_t w_floats;        /* floats of the weight arena (plain: = tab_elems) */
+  int64_t n_tiles;         /* aa: tiles of the whole batch (plain: 0) */
+  int32_t max_taps;        /* aa: the largest pitch of the batch (plain: taps) */
+  int32_t lds_floats;      /* aa: the largest tile_rows * cols_max * c_in of the batch (plain: 0) */
+  int32_t bad_image;       /* the first image one of whose axes needs more than TFIMM_RESIZE_AA_MAX_TAPS taps, or -1 */
+  int32_t reserved;
+} tfimm_resize_batch_sizes;
+
+/* The ONE place in C where records and tables of a mixed batch are built -- over tfimm_hip_resize_taps and
+ * tfimm_hip_resize_spans, which stay the only statements of the tap and span rules.  A plain host function: no GPU is needed
+ * or touched.  src_hw: [B][2] = (Hs, Ws); geometry: [B][4] = (Rh, Rw, top, left) (tfimm/models/factory.py resize_geometry);
+ * (H, W): the crop window; pad: the 4 border widths (t, b, l, r) of the output layout, or NULL for none -- c_in and pad
+ * enter the tile bookkeeping only; method 0 = bilinear, 1 = bicubic.  *sizes is always filled.  With recs == NULL nothing
+ * else is written (the sizing call); otherwise recs [B], tab_a and tab_b [tab_elems] (plain: idx and unused, may be NULL;
+ * aa: start and count) and w [w_floats] are filled -- each array at EXACTLY the reported size.  An image outside the
+ * antialias domain is named in sizes->bad_image and the call returns the invalid-argument code. */
+TFIMM_API int tfimm_hip_resize_batch_tables(int B, const int32_t* src_hw, const int32_t* geometry, int H, int W, int c_in,
+                                            const int32_t* pad, int method, int antialias, tfimm_resize_batch_sizes* sizes,
+                                            tfimm_resize_batch_rec* recs, int32_t* tab_a, int32_t* tab_b, float* w);
+TFIMM_API int tfimm_hip_preprocess_resize_batch(const tfimm_resize_batch_desc* d, void* stream);
+TFIMM_API int tfimm_hip_preprocess_resize_batch_aa(const tfimm_resize_batch_aa_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * tfimm_hip_layernorm: y[r][:] = (x[r][:] - mean) * rsqrt(var + eps) * gamma + beta,
  * population variance, fp32 statistics.  x row r starts at x + r*x_stride (elements),
  * y row r at y + r*y_stride.  Replaces tf.keras.layers.LayerNormalization
@@ -712,6 +814,9 @@ TFIMM_API int tfimm_hip_ref_cast_input(const void* in, int in_dtype, void* out, 
 TFIMM_API int tfimm_hip_ref_preprocess_resize(const tfimm_resize_desc* d, void* stream);
 /* tfimm_hip_preprocess_resize_aa with a float32 `out` */
 TFIMM_API int tfimm_hip_ref_preprocess_resize_aa(const tfimm_resize_aa_desc* d, void* stream);
+/* tfimm_hip_preprocess_resize_batch / _batch_aa with a float32 `out` (same descriptors, same device code) */
+TFIMM_API int tfimm_hip_ref_preprocess_resize_batch(const tfimm_resize_batch_desc* d, void* stream);
+TFIMM_API int tfimm_hip_ref_preprocess_resize_batch_aa(const tfimm_resize_batch_aa_desc* d, void* stream);
 TFIMM_API int tfimm_hip_ref_layernorm(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int d,
                                       int64_t x_stride, int64_t y_stride, float eps, void* stream);
 TFIMM_API int tfimm_hip_ref_patch_merge_ln(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W,

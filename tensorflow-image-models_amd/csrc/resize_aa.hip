@@ -19,6 +19,7 @@
 // in, so the result does not depend on the tiling.  All global offsets are 64-bit; every start + t is clamped into the image
 // and every LDS column into the staged range before use, so a bad table cannot read out of bounds.
 #include "common.h"
+#include "resize_tile.h"
 
 #include <cfloat>
 #include <cmath>
@@ -27,12 +28,10 @@
 
 namespace {
 
-constexpr int kTileRows = TFIMM_RESIZE_AA_TILE_ROWS;      // output rows of a tile, at most (fewer when LDS is short)
 constexpr int kTileCols = TFIMM_RESIZE_AA_TILE_COLS;      // output columns of a tile
 constexpr int kMaxBlocks = TFIMM_RESIZE_AA_MAX_BLOCKS;    // grid cap: workgroups stride over the tiles
 constexpr int kThreads = 256;
-// LDS budget of a workgroup: 64 KiB of float32, so two workgroups share a CU's 160 KiB with 32 KiB to spare
-constexpr int kLdsFloats = 64 * 1024 / 4;
+using tfimm_resize::kLdsFloats;   // the LDS budget of a workgroup and the tile rule: resize_tile.h
 
 struct ResizeAAArgs {
   const uint8_t* in;
@@ -144,17 +143,6 @@ __global__ void __launch_bounds__(kThreads) resize_aa_kernel(ResizeAAArgs a) {
   }
 }
 
-// Source columns that the x-spans of `n_cols` consecutive output columns can cover.  Consecutive span centres lie inv =
-// Ws / Rw apart and a span is at most x_taps long, so the range is (n_cols - 1) * inv + x_taps, plus 2 for the float32
-// rounding of the centres.  The descriptor does not carry Rw; inv <= Ws / W (the crop window is no wider than the resized
-// image) and inv <= (x_taps - 1) / 2 (x_taps >= 2 * radius * max(inv, 1) + 1 with radius >= 1, unless Ws caps it -- and then
-// Ws caps the range too) bound it.
-int span_cols(int n_cols, int Ws, int W, int x_taps) {
-  const double inv = fmin((double)Ws / (double)W, fmax((double)(x_taps - 1) * 0.5, 1.0));
-  const double cols = ceil((double)(n_cols - 1) * inv) + (double)x_taps + 2.0;
-  return cols < (double)Ws ? (int)cols : Ws;
-}
-
 int resize_aa_launch(const tfimm_resize_aa_desc* d, void* stream, bool f32, const char* who) {
   if (!d) TFIMM_FAIL(TFIMM_EINVAL, "%s: null descriptor", who);
   if (!d->in || !d->out || !d->y_start || !d->y_count || !d->y_w || !d->x_start || !d->x_count || !d->x_w || !d->mean_host ||
@@ -193,11 +181,8 @@ int resize_aa_launch(const tfimm_resize_aa_desc* d, void* stream, bool f32, cons
   if (!f32 && d->c_out == 4 && ((uintptr_t)d->out & 7) == 0) a.vec = 1;
   if (!f32 && d->c_out == 8 && ((uintptr_t)d->out & 15) == 0) a.vec = 2;
   // the tile: kTileCols output columns, and as many output rows (kTileRows at most) as the LDS budget holds of their
-  // vertical sums.  At the limits of the domain (x_taps = 64, c_in = 8) one row is 1043 x 8 floats = 33 KiB: always >= 1 row.
-  a.cols_max = span_cols(kTileCols, d->Ws, d->W, d->x_taps);
-  a.tile_rows = kLdsFloats / (a.cols_max * a.c_in);
-  if (a.tile_rows > kTileRows) a.tile_rows = kTileRows;
-  if (a.tile_rows > a.HP) a.tile_rows = a.HP;
+  // vertical sums (resize_tile.h)
+  a.tile_rows = tfimm_resize::tile_rows(d->Ws, d->W, d->x_taps, a.c_in, a.HP, &a.cols_max);
   if (a.tile_rows < 1) TFIMM_FAIL(TFIMM_EINVAL, "%s: a tile row of %d columns x %d channels exceeds the LDS budget", who, a.cols_max, a.c_in);
   a.tiles_y = (a.HP + a.tile_rows - 1) / a.tile_rows;
   a.tiles_x = (a.WP + kTileCols - 1) / kTileCols;

@@ -135,6 +135,42 @@ class ResizeAADesc(C.Structure):
                 ("y_taps", C.c_int32), ("x_taps", C.c_int32)]
 
 
+class ResizeBatchRec(C.Structure):
+    """tfimm_resize_batch_rec: where one image of a mixed-size batch and its tables live (csrc/resize_batch.hip)"""
+    _fields_ = [("in_offset", C.c_int64), ("Hs", C.c_int32), ("Ws", C.c_int32),
+                ("y_tab", C.c_int32), ("x_tab", C.c_int32), ("y_w", C.c_int32), ("x_w", C.c_int32),
+                ("y_taps", C.c_int32), ("x_taps", C.c_int32),
+                ("tile_rows", C.c_int32), ("cols_max", C.c_int32), ("tile0", C.c_int32), ("n_tiles", C.c_int32)]
+
+
+class ResizeBatchDesc(C.Structure):
+    """tfimm_resize_batch_desc: resize + centre crop + normalise of a uint8 batch of mixed sizes (csrc/resize_batch.hip)"""
+    _fields_ = [("in_", C.c_void_p), ("recs", C.c_void_p), ("out", C.c_void_p),
+                ("idx", C.c_void_p), ("w", C.c_void_p),
+                ("mean_host", C.POINTER(C.c_float)), ("std_host", C.POINTER(C.c_float)),
+                ("in_bytes", C.c_int64),
+                ("B", C.c_int32), ("c_in", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("c_out", C.c_int32),
+                ("pad_t", C.c_int32), ("pad_b", C.c_int32), ("pad_l", C.c_int32), ("pad_r", C.c_int32),
+                ("taps", C.c_int32)]
+
+
+class ResizeBatchAADesc(C.Structure):
+    """tfimm_resize_batch_aa_desc: the antialiased launch over a batch of mixed sizes (csrc/resize_batch.hip)"""
+    _fields_ = [("in_", C.c_void_p), ("recs", C.c_void_p), ("out", C.c_void_p),
+                ("start", C.c_void_p), ("count", C.c_void_p), ("w", C.c_void_p),
+                ("mean_host", C.POINTER(C.c_float)), ("std_host", C.POINTER(C.c_float)),
+                ("in_bytes", C.c_int64), ("w_floats", C.c_int64),
+                ("B", C.c_int32), ("c_in", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("c_out", C.c_int32),
+                ("pad_t", C.c_int32), ("pad_b", C.c_int32), ("pad_l", C.c_int32), ("pad_r", C.c_int32),
+                ("taps_cap", C.c_int32), ("lds_bytes", C.c_int32)]
+
+
+class ResizeBatchSizes(C.Structure):
+    """tfimm_resize_batch_sizes: what tfimm_hip_resize_batch_tables reports"""
+    _fields_ = [("in_bytes", C.c_int64), ("tab_elems", C.c_int64), ("w_floats", C.c_int64), ("n_tiles", C.c_int64),
+                ("max_taps", C.c_int32), ("lds_floats", C.c_int32), ("bad_image", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tfimm_hip.h
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -158,6 +194,10 @@ SYMBOLS = {
     "tfimm_hip_resize_span_taps": (_i, [_i, _i, _i]),
     "tfimm_hip_resize_spans": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "tfimm_hip_preprocess_resize_aa": (_i, [C.POINTER(ResizeAADesc), _vp]),
+    "tfimm_hip_resize_batch_tables": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), _i, _i,
+                                           C.POINTER(ResizeBatchSizes), _vp, _vp, _vp, _vp]),
+    "tfimm_hip_preprocess_resize_batch": (_i, [C.POINTER(ResizeBatchDesc), _vp]),
+    "tfimm_hip_preprocess_resize_batch_aa": (_i, [C.POINTER(ResizeBatchAADesc), _vp]),
     "tfimm_hip_row_stats": (_i, [_vp, _vp, _i64, _i, _i64, _f, _vp]),
     "tfimm_hip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
     "tfimm_hip_attention": (_i, [C.POINTER(AttnDesc), _vp]),
@@ -189,6 +229,8 @@ SYMBOLS = {
     "tfimm_hip_ref_cast_input": (_i, [_vp, _i, _vp, _i64, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
     "tfimm_hip_ref_preprocess_resize": (_i, [C.POINTER(ResizeDesc), _vp]),
     "tfimm_hip_ref_preprocess_resize_aa": (_i, [C.POINTER(ResizeAADesc), _vp]),
+    "tfimm_hip_ref_preprocess_resize_batch": (_i, [C.POINTER(ResizeBatchDesc), _vp]),
+    "tfimm_hip_ref_preprocess_resize_batch_aa": (_i, [C.POINTER(ResizeBatchAADesc), _vp]),
     "tfimm_hip_ref_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
     "tfimm_hip_ref_patch_merge_ln": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "tfimm_hip_ref_copy_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -326,6 +368,53 @@ def resize_aa_tables(src_hw, geometry, size, method: str):
                              f"more than TFIMM_RESIZE_AA_MAX_TAPS = {RESIZE_AA_MAX_TAPS}: the source is too large for the "
                              "device resize, shrink it on the host first")
     return resize_spans(Hs, Rh, top, H, method), resize_spans(Ws, Rw, left, W, method)
+
+
+#: numpy view of tfimm_resize_batch_rec
+RESIZE_BATCH_REC = [("in_offset", "<i8")] + [(n, "<i4") for n in (
+    "Hs", "Ws", "y_tab", "x_tab", "y_w", "x_w", "y_taps", "x_taps", "tile_rows", "cols_max", "tile0", "n_tiles")]
+
+
+def resize_batch_tables(sizes, geometries, size, method: str, antialias: bool = False, *, c_in: int = 3, pad=(0, 0, 0, 0)):
+    """tfimm_hip_resize_batch_tables as numpy arrays -- records and table arenas of a batch whose images each have a size of
+    their own (``sizes[i] = (Hs, Ws)``, ``geometries[i] = (Rh, Rw, top, left)``), all going to the crop window ``size``; a host
+    function, no GPU involved.  Returns a dict: ``recs`` (structured, ``RESIZE_BATCH_REC``), ``idx`` and ``w`` (plain) or
+    ``start``, ``count`` and ``w`` (antialiased), each exactly as long as the library asked for, and the reported ``in_bytes``,
+    ``max_taps``, ``lds_floats`` and ``n_tiles``.  ``c_in`` and ``pad`` (the output layout's border) enter the byte offsets
+    and the tile bookkeeping only.  ``ValueError`` naming the image when one lies outside the antialias domain."""
+    import numpy as np
+    src = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(-1, 2))
+    geo = np.ascontiguousarray(np.asarray(geometries, np.int32).reshape(-1, 4))
+    B = src.shape[0]
+    if B == 0 or geo.shape[0] != B:
+        raise ValueError(f"resize_batch_tables: {B} sizes and {geo.shape[0]} geometries")
+    pads = (C.c_int32 * 4)(*[int(v) for v in pad])
+    i32p = C.POINTER(C.c_int32)
+    args = (B, src.ctypes.data_as(i32p), geo.ctypes.data_as(i32p), int(size[0]), int(size[1]), int(c_in), pads,
+            RESIZE_METHODS[method], 1 if antialias else 0)
+    need = ResizeBatchSizes()
+    rc = lib.tfimm_hip_resize_batch_tables(*args, C.byref(need), None, None, None, None)
+    if rc != 0 and need.bad_image >= 0:
+        i = need.bad_image
+        raise ValueError(f"antialiased {method} resize: image {i} of the batch ({src[i, 0]} x {src[i, 1]} -> {geo[i, 0]} x "
+                         f"{geo[i, 1]}) needs more than TFIMM_RESIZE_AA_MAX_TAPS = {RESIZE_AA_MAX_TAPS} taps per output pixel: "
+                         "the source is too large for the device resize, shrink it on the host first")
+    check(rc, "tfimm_hip_resize_batch_tables")
+    recs = np.zeros(B, np.dtype(RESIZE_BATCH_REC))
+    assert recs.itemsize == C.sizeof(ResizeBatchRec)
+    tab_a = np.zeros(need.tab_elems, np.int32)
+    tab_b = np.zeros(need.tab_elems if antialias else 0, np.int32)
+    w = np.zeros(need.w_floats, np.float32)
+    check(lib.tfimm_hip_resize_batch_tables(*args, C.byref(need), recs.ctypes.data, tab_a.ctypes.data,
+                                            tab_b.ctypes.data if antialias else None, w.ctypes.data),
+          "tfimm_hip_resize_batch_tables")
+    out = {"recs": recs, "w": w, "in_bytes": int(need.in_bytes), "max_taps": int(need.max_taps),
+           "lds_floats": int(need.lds_floats), "n_tiles": int(need.n_tiles)}
+    if antialias:
+        out["start"], out["count"] = tab_a, tab_b
+    else:
+        out["idx"] = tab_a
+    return out
 
 
 def check(rc: int, what: str = ""):

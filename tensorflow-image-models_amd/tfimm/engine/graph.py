@@ -1112,6 +1112,26 @@ class Builder:
         return out
 
 
+class _Mixed:
+    """The input of ``Plan.run`` / ``Plan.capture`` for a batch of mixed-size images: the pixels are not an argument, they
+    are what ``Plan.stage_mixed`` last put into the plan's own buffers."""
+    dtype = "torch.uint8"
+
+    def __repr__(self):
+        return "MIXED"
+
+
+MIXED = _Mixed()
+
+
+def _grown(need: int, have: int, floor: int) -> int:
+    """capacity after growth by doubling: the smallest ``floor * 2 ** k`` that holds ``need`` (``have`` when it does)"""
+    cap = max(have, floor)
+    while cap < need:
+        cap *= 2
+    return cap
+
+
 # ---------------------------------------------------------------------------------------
 # Plan: a program bound to device buffers for one batch size
 # ---------------------------------------------------------------------------------------
@@ -1144,6 +1164,9 @@ class Plan:
         #: resizing input step; ``norm`` carries the antialias flag
         #: (launch_input), built once per source size and kept on the device
         self._resize_tabs: Dict[tuple, tuple] = {}
+        #: norm -> the state of the mixed-size input step (``stage_mixed``): descriptor, device buffers for the pixel arena,
+        #: the records and the tables, their capacities
+        self._mixed: Dict[tuple, dict] = {}
         self._gemm_descs = []
         self._gemm_call_index = []
         self._tune_times = {}          # shape key -> {hint: ms} of the last isolated autotune
@@ -1580,7 +1603,7 @@ class Plan:
         import torch
         if self.prog.precision == "fp32":
             raise NotImplementedError("plans of the float32 verification path are not exported")
-        if self._resize_tabs:
+        if self._resize_tabs or self._mixed:
             raise NotImplementedError("plans run with a resize spec are not exported: tfimm_hip_plan_forward takes float32 / "
                                       "bf16 images of the program's input size only")
         if self.device == "cpu":
@@ -1751,6 +1774,11 @@ class Plan:
         (tfimm_hip_preprocess_resize_aa)."""
         import torch
         c_in = self._input_patch[3]
+        if x_dev is MIXED:
+            if self.prog.precision != "fp32" and self._stem_raw is not None:
+                d, padded_ptr = self._stem_raw[:2]          # the fused stem reads the converted copy, as for every uint8 input
+                d.x, d.in_dtype = padded_ptr, 0
+            return self._launch_mixed(st, norm)
         if (x_dev.dtype == torch.uint8) != (norm is not None):
             raise TypeError("uint8 input needs norm=(mean, std); float input must not pass it")
         resize = None
@@ -1835,6 +1863,96 @@ class Plan:
         d.in_ = x_dev.data_ptr()
         fn = "tfimm_hip_ref_preprocess_resize" if self.prog.precision == "fp32" else "tfimm_hip_preprocess_resize"
         return getattr(ffi.lib, fn + ("_aa" if aa else ""))(C.byref(d), st)
+
+    def stage_mixed(self, images, norm) -> bool:
+        """The host half of the mixed-size input step (tfimm_hip_preprocess_resize_batch[_aa]): ``images`` is a
+        list of ``self.batch`` contiguous uint8 arrays (Hs_i, Ws_i, C), ``norm = (mean, std, (interpolation, crop_pct[,
+        True]))``.  Builds records and tables with the library's host function, packs the pixels back to back into a pinned
+        staging buffer and uploads both (two copies on the current stream) into buffers this plan owns.  The launch --
+        ``run(MIXED, norm=norm)`` or a recording of it -- reads those buffers and nothing else.  Capacities (pixel arena,
+        weight arena, span pitch, LDS) grow by doubling; returns True when one grew, i.e. when a recording of this step no
+        longer points at the live buffers.  ``ValueError`` before anything is uploaded when an image lies outside the
+        antialias domain."""
+        import torch
+        from ..models.factory import resize_geometry
+        ffi = self.ffi
+        mean, std, (method, crop_pct, *aa) = norm
+        aa = bool(aa and aa[0])
+        H, W, _ = self.prog.input_shape
+        c_in = self._input_patch[3]
+        if len(images) != self.batch or any(im.ndim != 3 or im.shape[2] != c_in or im.dtype != np.uint8 for im in images):
+            raise ValueError(f"mixed resize input of {len(images)} images for a plan of batch {self.batch}, {c_in} channels")
+        fp32 = self.prog.precision == "fp32"
+        pad = (0, 0, 0, 0) if fp32 else tuple(self._input_pad)
+        sizes = [im.shape[:2] for im in images]
+        tabs = ffi.resize_batch_tables(sizes, [resize_geometry(s, (H, W), crop_pct) for s in sizes], (H, W), method, aa,
+                                       c_in=c_in, pad=pad)
+        st = self._mixed.get(norm)
+        grew = False
+        if st is None:
+            d = ffi.ResizeBatchAADesc() if aa else ffi.ResizeBatchDesc()
+            host = ((C.c_float * c_in)(*[float(v) for v in mean]), (C.c_float * c_in)(*[float(v) for v in std]))
+            d.mean_host, d.std_host = host
+            d.out = self._input_patch[1]
+            d.B, d.c_in, d.H, d.W, d.c_out = self.batch, c_in, H, W, self._input_patch[4]
+            d.pad_t, d.pad_b, d.pad_l, d.pad_r = pad
+            if not aa:
+                d.taps = 4 if method == "bicubic" else 2
+            st = self._mixed[norm] = {"desc": d, "host": host, "aa": aa, "arena_cap": 0, "w_cap": 0, "taps_cap": 0, "lds_cap": 0}
+            grew = True
+        d = st["desc"]
+        # -- capacities: doubling, so that a stream of batches settles after a few growths
+        arena_cap = _grown(tabs["in_bytes"], st["arena_cap"], 1 << 16)
+        w_cap = _grown(tabs["w"].size, st["w_cap"], 1 << 14)
+        if arena_cap != st["arena_cap"]:
+            st["arena"] = torch.empty(arena_cap, dtype=torch.uint8, device=self.device)
+            st["stage"] = torch.empty(arena_cap, dtype=torch.uint8, pin_memory=self.device != "cpu")
+            st["arena_cap"], grew = arena_cap, True
+            d.in_, d.in_bytes = st["arena"].data_ptr(), arena_cap
+        n_rec = self.batch * C.sizeof(ffi.ResizeBatchRec)
+        n_tab = tabs["idx"].size if not aa else tabs["start"].size
+        if w_cap != st["w_cap"]:
+            # one buffer: records | idx (or start | count) | weights -- everything but the weights has a fixed size
+            n_meta = n_rec + 4 * n_tab * (2 if aa else 1) + 4 * w_cap
+            st["meta"] = torch.empty(n_meta, dtype=torch.uint8, device=self.device)
+            st["meta_stage"] = torch.empty(n_meta, dtype=torch.uint8, pin_memory=self.device != "cpu")
+            st["w_cap"], grew = w_cap, True
+            base = st["meta"].data_ptr()
+            d.recs = base
+            if aa:
+                d.start, d.count, d.w, d.w_floats = base + n_rec, base + n_rec + 4 * n_tab, base + n_rec + 8 * n_tab, w_cap
+            else:
+                d.idx, d.w = base + n_rec, base + n_rec + 4 * n_tab
+        if aa:
+            taps_cap = min(_grown(tabs["max_taps"], st["taps_cap"], 16), ffi.RESIZE_AA_MAX_TAPS)
+            lds_cap = min(_grown(4 * tabs["lds_floats"], st["lds_cap"], 16 << 10), 64 << 10)
+            if (taps_cap, lds_cap) != (st["taps_cap"], st["lds_cap"]):
+                st["taps_cap"], st["lds_cap"], grew = taps_cap, lds_cap, True
+                d.taps_cap, d.lds_bytes = taps_cap, lds_cap
+        # -- pack and upload: the pixels back to back in list order (the offsets of the records), then records and tables
+        stage, pos = st["stage"].numpy(), 0
+        for im in images:
+            stage[pos:pos + im.size] = im.reshape(-1)
+            pos += im.size
+        assert pos == tabs["in_bytes"]
+        st["arena"][:pos].copy_(st["stage"][:pos], non_blocking=True)
+        parts = [tabs["recs"]] + ([tabs["start"], tabs["count"]] if aa else [tabs["idx"]]) + [tabs["w"]]
+        meta, pos = st["meta_stage"].numpy(), 0
+        for a in parts:
+            meta[pos:pos + a.nbytes] = a.view(np.uint8).reshape(-1)
+            pos += a.nbytes
+        st["meta"][:pos].copy_(st["meta_stage"][:pos], non_blocking=True)
+        # the staging buffers are rewritten by the next call: the copies must have left them
+        torch.cuda.current_stream().synchronize() if self.device != "cpu" else None
+        return grew
+
+    def _launch_mixed(self, st, norm) -> int:
+        """the device half: one launch over whatever ``stage_mixed`` last uploaded; the float32 path calls the ``_ref_`` twin"""
+        m = self._mixed.get(norm)
+        if m is None:
+            raise RuntimeError("run(MIXED) before stage_mixed: the plan holds no mixed batch for this norm")
+        fn = "tfimm_hip_ref_preprocess_resize_batch" if self.prog.precision == "fp32" else "tfimm_hip_preprocess_resize_batch"
+        return getattr(self.ffi.lib, fn + ("_aa" if m["aa"] else ""))(C.byref(m["desc"]), st)
 
     def run(self, x_dev, stream_ptr: Optional[int] = None, norm=None, lo: int = 0, hi: Optional[int] = None):
         """Enqueue the whole program on the current torch stream.  ``x_dev``: contiguous cuda

@@ -126,7 +126,15 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
     (tfimm_hip_preprocess_resize_aa), ``pre(img).numpy()`` again the same arithmetic bit for bit.  An axis
     may shrink to about 1/15 (bicubic) or 1/31 (bilinear) of its size; beyond that ``model(pre(img))`` raises
     ``ValueError`` (TFIMM_RESIZE_AA_MAX_TAPS).  Antialiased and plain input of the same source size use separate plans and
-    recordings."""
+    recordings.
+
+    A LIST (or tuple) of uint8 images ``(Hs_i, Ws_i, C)`` with ``resize=True``: every image may have a size of its own.  The
+    ``DeferredInput`` holds the list (``shape`` is ``(B, None, None, C)``), ``numpy()`` is the stack of the per-image results,
+    and ``model(pre(images))`` resizes the whole list in ONE launch whose arguments do not depend on the sizes
+    (tfimm_hip_preprocess_resize_batch[_aa]): per model, batch size and precision there is one plan and one
+    recording for every mix of sizes, so streaming a folder of photos does not grow device memory with the number of
+    sizes.  Same arithmetic as for an array, image by image, bit for bit.  A list without ``resize=True``, an empty list, a
+    member that is not uint8, not 3-D or of another channel count raises ``ValueError``."""
     if not is_model(model_name):
         raise ValueError(f"Unknown model: {model_name}.")
     cfg = model_config(model_name)
@@ -147,7 +155,26 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
 
     mean, std = _adapt(cfg.mean), _adapt(cfg.std)
 
+    def _images(imgs):
+        """a list / tuple of images, each of a size of its own: one DeferredInput over the list"""
+        from .model import DeferredInput
+        if not resize:
+            raise ValueError("a list of images needs create_preprocessing(defer=True, resize=True): images of different "
+                             "sizes only meet in the device resize; stack same-sized images into one array instead")
+        if len(imgs) == 0:
+            raise ValueError("create_preprocessing(resize=True): an empty list of images")
+        for i, im in enumerate(imgs):
+            if not str(getattr(im, "dtype", "")).endswith("uint8"):
+                raise ValueError(f"create_preprocessing(resize=True) takes uint8 images only, image {i} of the list is "
+                                 f"{getattr(im, 'dtype', type(im).__name__)}: there is no host resize path")
+            if len(im.shape) != 3 or int(im.shape[2]) != n or min(int(v) for v in im.shape) <= 0:
+                raise ValueError(f"image {i} of the list has shape {tuple(im.shape)}, expected (Hs, Ws, {n})")
+        spec = (cfg.interpolation, float(cfg.crop_pct), tuple(int(v) for v in cfg.input_size)) + ((True,) if antialias else ())
+        return DeferredInput(list(imgs), mean.astype(np.float32), std.astype(np.float32), resize=spec)
+
     def _preprocess(img):
+        if isinstance(img, (list, tuple)) and (len(img) == 0 or hasattr(img[0], "shape")):
+            return _images(img)
         if defer and getattr(img, "dtype", None) is not None and str(img.dtype).endswith("uint8"):
             from .model import DeferredInput
             spec = (cfg.interpolation, float(cfg.crop_pct), tuple(int(v) for v in cfg.input_size)) if resize else None

@@ -81,7 +81,14 @@ class DeferredInput:
             self.resize += (True,)
 
     @property
+    def mixed(self) -> bool:
+        """a list of images, each of a size of its own (``create_preprocessing(..., resize=True)`` on a list)"""
+        return isinstance(self.data, (list, tuple))
+
+    @property
     def shape(self):
+        if self.mixed:
+            return (len(self.data), None, None, int(self.data[0].shape[2]))
         return tuple(self.data.shape)
 
     def numpy(self) -> np.ndarray:
@@ -91,7 +98,9 @@ class DeferredInput:
         horizontal, each sum from 0.0 in tap order; bilinear: TensorFlow's compute_lerp -- then the three operations of
         the normalisation, all in float32.  Downscaling is not antialiased unless the spec says so: then the sums run
         over the span tables of tfimm_hip_resize_spans (``tf.image.resize(..., antialias=True)``), vertical pass first,
-        each sum from 0.0 in tap order, for both methods."""
+        each sum from 0.0 in tap order, for both methods.  A list of images: the stack of every image's own result."""
+        if self.mixed:
+            return np.stack([DeferredInput(im, self.mean, self.std, self.resize).numpy() for im in self.data])
         d = self.data
         d = d.cpu().numpy() if hasattr(d, "cpu") else np.asarray(d)
         x = d.astype(np.float32)
@@ -253,6 +262,16 @@ class Model:
 
     def _to_device(self, x):
         import torch
+        if isinstance(x, DeferredInput) and x.mixed:
+            # a list of images of mixed sizes stays on the host: the plan packs it into its staging buffer per call
+            imgs = [np.ascontiguousarray(im.cpu().numpy() if hasattr(im, "cpu") else im) for im in x.data]
+            if x.resize is None or not imgs or len(x.mean) != self.cfg.in_channels or any(
+                    im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != self.cfg.in_channels or im.size == 0 for im in imgs):
+                raise ValueError(f"{self.name}: expected a non-empty list of uint8 images (Hs, Ws, {self.cfg.in_channels}) with "
+                                 f"a resize spec, got shapes {[tuple(im.shape) for im in imgs]}")
+            if not torch.cuda.is_available():
+                raise RuntimeError("tfimm (MI355X engine) needs a ROCm GPU: no CPU execution path exists.")
+            return imgs
         if isinstance(x, DeferredInput):
             # uint8 pixels + (mean, std): the normalisation runs inside the engine's input conversion
             u = x.data if isinstance(x.data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x.data))
@@ -280,6 +299,8 @@ class Model:
         import torch
         xd = self._to_device(x)
         norm = (tuple(x.mean), tuple(x.std)) if isinstance(x, DeferredInput) else None
+        if isinstance(xd, list):
+            return self._run_mixed(xd, norm, x.resize, want_features)
         B, H, W, _ = xd.shape
         src = ()
         if norm is not None and x.resize is not None:
@@ -320,6 +341,53 @@ class Model:
                 plan.run(chunk, norm=norm)
             for name, t in prog.outputs.items():
                 # plans own their buffers and reuse them on the next call: hand out copies
+                results[name].append(plan.tensor_view(t).clone())
+        out = {}
+        for name, parts in results.items():
+            v = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+            t = prog.outputs[name]
+            if t.H > 0:
+                v = v.view(v.shape[0], t.H, t.W, t.C)
+            elif t.rows == 1:
+                v = v.view(v.shape[0], t.C)
+            out[name] = v
+        return out
+
+    def _run_mixed(self, imgs, norm, resize, want_features: bool):
+        """A list of uint8 images, each of a size of its own.  The program is the one of the model's input
+        size; the keys carry ``("src", "mixed")`` in place of a source size, so every mix of sizes meets the same plan and the
+        same recording.  Per chunk: the plan builds records and tables on the host and uploads them with the packed pixels
+        (``Plan.stage_mixed``), then the program is launched or replayed -- the recording reads the plan's buffers, whatever
+        they hold.  Only a buffer that had to grow drops the recording.  ``branches`` is not used: a mixed batch runs on one
+        branch (same bits, the engine's kernels never mix images)."""
+        import torch
+        from ..engine.graph import MIXED
+        method, crop_pct, (H, W) = resize[:3]
+        aa = len(resize) > 3
+        norm = norm + ((method, crop_pct) + ((True,) if aa else ()),)
+        src = (("src", "mixed") + (("antialias",) if aa else ()),)
+        prog = self.program(H, W, want_features)
+        B = len(imgs)
+        mb = min(self.micro_batch or B, B)
+        results: Dict[str, list] = {k: [] for k in prog.outputs}
+        for start in range(0, B, mb):
+            nb = min(mb, B - start)
+            key = (H, W, bool(want_features), nb, precision.get()) + src
+            plan = self._plans.get(key)
+            if plan is None:
+                plan = self._plans[key] = prog.make_plan(nb)
+            gkey = key + ("torch.uint8", norm)
+            if plan.stage_mixed(imgs[start:start + nb], norm):
+                self._captured.pop(gkey, None)        # a buffer grew: the recording points at the old one
+            cap = self._captured.get(gkey)
+            if cap is None and self._plan_uses.get(gkey, 0) >= 1 and os.environ.get("TFIMM_NO_GRAPH", "0") != "1":
+                cap = self._captured[gkey] = plan.capture(MIXED, norm)
+            self._plan_uses[gkey] = self._plan_uses.get(gkey, 0) + 1
+            if cap is not None:
+                cap.replay()
+            else:
+                plan.run(MIXED, norm=norm)
+            for name, t in prog.outputs.items():
                 results[name].append(plan.tensor_view(t).clone())
         out = {}
         for name, parts in results.items():
