@@ -794,6 +794,29 @@ typedef struct tfimm_gemm_mx_desc {
 TFIMM_API int tfimm_hip_gemm_mx(const tfimm_gemm_mx_desc* d, void* stream);
 
 /* =======================================================================================
+ * OUTPUT END (csrc/topk.hip): top-k classes and their softmax probabilities of float32 logits
+ * ======================================================================================= */
+
+/* tfimm_hip_topk: per row of logits [B][ld] (float32, N <= ld valid columns) the k largest entries.
+ *   values  float32 [B][k]  the selected logits, bit for bit
+ *   indices int32   [B][k]  their columns
+ *   probs   float32 [B][k]  exp(v - m) / sum_i exp(x_i - m), m the row maximum, the sum over all N columns; may be NULL.
+ *                           Specified for rows whose entries are all finite; for other rows it may hold anything.
+ * Order (tf.math.top_k): by value descending, compared as floats; equal values by ascending column.  -0.0 == +0.0 (the
+ * column decides).  A NaN orders above +inf whatever its sign or payload, NaNs among themselves by column: a poisoned row
+ * shows in the answer.  tests/topk_ref.py restates the rule on the CPU.
+ * One workgroup of 256 threads per row; the row is read once and kept in LDS, hence N <= TFIMM_TOPK_MAX_N; k selection
+ * rounds, k <= TFIMM_TOPK_MAX_K.  No alignment is required (16-byte loads where base and ld allow, scalar otherwise); offsets
+ * are 64-bit; no atomics, no scratch memory; every reduction has a fixed order: results are bit-reproducible and a row's
+ * result does not depend on B.  B == 0 launches nothing.  The logits are float32 under every precision mode, so there is no
+ * tfimm_hip_ref_* twin.
+ * Replaces, behind `model(x)` in a caller of the reference: tf.nn.softmax(logits) + tf.math.top_k(probs, k). */
+#define TFIMM_TOPK_MAX_K 64
+#define TFIMM_TOPK_MAX_N 32768
+TFIMM_API int tfimm_hip_topk(const float* logits, int64_t ld, int B, int N, int k, float* values, int32_t* indices,
+                             float* probs, void* stream);
+
+/* =======================================================================================
  * FLOAT32 VERIFICATION PATH (csrc/ref32.hip; selected by TFIMM_PRECISION=fp32, tfimm/engine/precision.py)
  *
  * The reference is float32 end to end and pins values at 1e-3 relative to the maximum (tests/test_timm.py:71).  The
@@ -860,8 +883,10 @@ TFIMM_API int tfimm_hip_ref_class_attention(const void* q, const void* kv, void*
  *   tfimm_hip_plan_create   upload the constants into `workspace` (synchronises `stream` once; the blob may be freed
  *                           afterwards) and resolve every pointer of the call list
  *   tfimm_hip_plan_forward  input: [batch][in_h][in_w][in_c] NHWC, in_dtype 0 = float32, 1 = bf16 (device pointer)
- *   tfimm_hip_plan_output   where a named result lies ("logits", or a feature name of a plan exported with features):
- *                           device pointer into the workspace, rows (= batch * rows per image), columns, dtype (0 bf16, 1 f32)
+ *   tfimm_hip_plan_output   where a named result lies ("logits", a feature name of a plan exported with features, or
+ *                           "topk_values" / "topk_indices" / "topk_probs" of a plan exported with top_k):
+ *                           device pointer into the workspace, rows (= batch * rows per image), columns, dtype (0 bf16, 1 f32,
+ *                           2 int32)
  * A plan object is not re-entrant (one forward at a time); distinct plans are independent.
  * ======================================================================================= */
 typedef void* tfimm_plan_t;

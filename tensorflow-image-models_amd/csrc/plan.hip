@@ -119,6 +119,7 @@ const std::map<std::string, Entry>& table() {
       TFIMM_ADAPTER(tfimm_hip_eca_gate, fp, float, fp, float*, int, int, int, int),
       TFIMM_ADAPTER(tfimm_hip_grouped_conv3x3, vp, vp, fp, mp, int, int, int, int, int, int),
       TFIMM_ADAPTER(tfimm_hip_bias_act, vp, fp, mp, int64_t, int, int),
+      TFIMM_ADAPTER(tfimm_hip_topk, fp, int64_t, int, int, int, float*, int32_t*, float*),
   };
   return t;
 }
@@ -227,10 +228,11 @@ int parse(const void* blob, size_t bytes, Plan& pl) {
         pl.structs[pl.stem_struct].bytes.size() < sizeof(tfimm_stem_desc))
       TFIMM_FAIL(TFIMM_EINVAL, "plan: bad stem reference");
   }
-  // an output is rows_per_image x batch rows of `cols` elements (bf16 or fp32) starting at `offset`: the whole extent inside its slab
+  // an output is rows_per_image x batch rows of `cols` elements (bf16, fp32 or int32) starting at `offset`: the whole extent inside its slab
   for (const auto& o : pl.outputs) {
     if (o.slab >= pl.slab_off.size()) TFIMM_FAIL(TFIMM_EINVAL, "plan: output '%s' outside its slab", o.name.c_str());
-    const uint64_t cap = pl.slab_bytes[o.slab], esz = o.dtype == 1 ? 4 : 2;
+    if (o.dtype > 2) TFIMM_FAIL(TFIMM_EINVAL, "plan: output '%s' has dtype code %u (0 bf16, 1 fp32, 2 int32)", o.name.c_str(), o.dtype);
+    const uint64_t cap = pl.slab_bytes[o.slab], esz = o.dtype == 0 ? 2 : 4;
     // every product is checked by DIVISION before it is formed: rows_per_image < 2^40 times an unbounded 32-bit batch, or
     // rows times cols, wrap in 64 bits (rows = cols = 2^32 gives 0 and passed the multiplied form of this check)
     bool ok = o.offset < cap && o.cols > 0 && o.rows_per_image > 0 && pl.batch > 0 && o.cols <= kMaxBuf && o.rows_per_image <= kMaxBuf / pl.batch;

@@ -6,6 +6,7 @@ Drop-in for the inference path of martinsbruveris/tensorflow-image-models:
 """
 from . import architectures, layers  # noqa: F401
 from .models.factory import create_model, create_preprocessing  # noqa: F401
+from .models.model import Tensor, TopK  # noqa: F401
 from .models.registry import list_models  # noqa: F401
 from .utils import (  # noqa: F401
     cached_model_path,

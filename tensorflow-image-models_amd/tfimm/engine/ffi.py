@@ -218,6 +218,8 @@ SYMBOLS = {
     "tfimm_hip_eca_gate": (_i, [_vp, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
     "tfimm_hip_grouped_conv3x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "tfimm_hip_bias_act": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
+    # the output end (csrc/topk.hip): logits, ld, B, N, k, values, indices, probs
+    "tfimm_hip_topk": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     # program-level entry points (csrc/plan.hip): a serialised plan (graph.Plan.export) run without Python host logic
     "tfimm_hip_plan_query": (_i, [_vp, C.c_size_t, _vp]),
     "tfimm_hip_plan_create": (_i, [_vp, C.c_size_t, _vp, _vp, C.POINTER(_vp)]),
@@ -329,6 +331,10 @@ def resize_taps(n_in: int, n_resized: int, first: int, n_out: int, method: str):
 # include/tfimm_hip.h: the domain and the tiling of tfimm_hip_preprocess_resize_aa
 RESIZE_AA_MAX_TAPS = 64
 RESIZE_AA_TILE_ROWS, RESIZE_AA_TILE_COLS, RESIZE_AA_MAX_BLOCKS = 16, 32, 1024
+
+
+# include/tfimm_hip.h: the domain of tfimm_hip_topk (k selection rounds over a row held in LDS)
+TOPK_MAX_K, TOPK_MAX_N = 64, 32768
 
 
 def resize_span_taps(n_in: int, n_resized: int, method: str) -> int:

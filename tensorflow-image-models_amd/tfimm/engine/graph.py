@@ -33,14 +33,14 @@ class TRef:
     C: int
     H: int = 0
     W: int = 0
-    dtype: str = "bf16"    # "bf16" | "f32" | "mx" (MXFP8: e4m3 [rows][mx_ld] followed by E8M0 scales [rows][mx_ld / 32])
+    dtype: str = "bf16"    # "bf16" | "f32" | "i32" | "mx" (MXFP8: e4m3 [rows][mx_ld] followed by E8M0 scales [rows][mx_ld / 32])
     keep: bool = False     # never recycle the buffer (outputs / returned features)
     # a view onto another tensor's buffer: (parent id, element offset per image-row stride)
     name: str = ""
 
     @property
     def itemsize(self) -> int:
-        return {"bf16": 2, "f32": 4, "mx": 1}[self.dtype]
+        return {"bf16": 2, "f32": 4, "i32": 4, "mx": 1}[self.dtype]
 
     @property
     def mx_ld(self) -> int:
@@ -1105,6 +1105,36 @@ class Builder:
         p.add("patch_merge_ln", [x], out, consts, cite=cite, H=x.H, W=x.W, C=x.C, eps=float(eps))
         return out
 
+    def topk(self, logits: TRef, k: int, probs=True, heads: int = 1, cite="tf.nn.softmax + tf.math.top_k behind model(x)"):
+        """The ``k`` largest logits of every image, their columns and their softmax probabilities (tfimm_hip_topk): one op
+        behind the program's ``logits``, which stay an output.  Marks ``topk_values`` (f32), ``topk_indices`` (i32) and --
+        with ``probs`` -- ``topk_probs`` (f32) as program outputs, each ``rows = 1, C = k``.  ``heads > 1``: the logits
+        tensor holds that many heads side by side (the two of a distilled DeiT, vit.py:474-476); every head is a row of its
+        own and the outputs have ``rows = heads``.  Returns the three tensors (``None`` in place of absent probs)."""
+        from . import ffi
+        p = self.p
+        k, heads = int(k), int(heads)
+        if logits.dtype != "f32":
+            raise ValueError(f"topk reads float32 logits, got a {logits.dtype} tensor (a model without classifier has none)")
+        assert heads >= 1 and logits.C % heads == 0, (logits.C, heads)
+        N = logits.C // heads
+        if N > ffi.TOPK_MAX_N:
+            raise ValueError(f"topk: {N} classes, more than TFIMM_TOPK_MAX_N = {ffi.TOPK_MAX_N} (the row is held in LDS)")
+        if not 1 <= k <= min(N, ffi.TOPK_MAX_K):
+            raise ValueError(f"topk: k={k}, must be in [1, min({N} classes, TFIMM_TOPK_MAX_K = {ffi.TOPK_MAX_K})]")
+        rows = logits.rows * heads
+        values = p.new_tensor(rows, k, dtype="f32", name="topk_values")
+        indices = p.new_tensor(rows, k, dtype="i32", name="topk_indices")
+        pr = p.new_tensor(rows, k, dtype="f32", name="topk_probs") if probs else None
+        # ld: the real distance between two rows the kernel reads -- the logits tensor's row, or one head of it
+        p.add("topk", [logits], values, cite=cite, extra_outputs=[indices] + ([pr] if probs else []),
+              rows=rows, N=N, k=k, ld=logits.C // heads, probs=bool(probs))
+        p.mark_output("topk_values", values)
+        p.mark_output("topk_indices", indices)
+        if probs:
+            p.mark_output("topk_probs", pr)
+        return values, indices, pr
+
     def reshape(self, x: TRef, rows: int, C: int, H=0, W=0) -> TRef:
         """Free reinterpretation of a contiguous tensor (tf.reshape)."""
         assert rows * C == x.rows * x.C
@@ -1199,6 +1229,8 @@ class Plan:
         n = self.batch * t.rows * t.C
         if t.dtype == "f32":
             return slab[: n * 4].view(torch.float32).view(self.batch, t.rows, t.C)
+        if t.dtype == "i32":
+            return slab[: n * 4].view(torch.int32).view(self.batch, t.rows, t.C)
         return slab[: n * 2].view(torch.bfloat16).view(self.batch, t.rows, t.C)
 
     # build ---------------------------------------------------------------------------------------
@@ -1457,11 +1489,17 @@ class Plan:
                 self.calls.append((lib.tfimm_hip_patch_merge_ln,
                                    (self.tptr(op.inputs[0]), self.tptr(op.output), self.cptr(op.consts["gamma"]),
                                     self.cptr(op.consts["beta"]), B, a["H"], a["W"], a["C"], a["eps"])))
+            elif k == "topk":
+                # logits are float32 under every precision: the same kernel on all three paths (_FP32_SHARED)
+                pr = self.tptr(op.extra_outputs[1]) if a["probs"] else None
+                self.calls.append((lib.tfimm_hip_topk,
+                                   (self.tptr(op.inputs[0]), a["ld"], B * a["rows"], a["N"], a["k"], self.tptr(op.output),
+                                    self.tptr(op.extra_outputs[0]), pr)))
             else:
                 raise NotImplementedError(k)
 
     # kernels that are float32 on both paths
-    _FP32_SHARED = ("tfimm_hip_se_gate", "tfimm_hip_eca_gate")
+    _FP32_SHARED = ("tfimm_hip_se_gate", "tfimm_hip_eca_gate", "tfimm_hip_topk")
 
     def _bind_fp32(self):
         """Verification path (engine/precision.py): every call of the list goes to the float32 kernel of the same name
@@ -1709,7 +1747,7 @@ class Plan:
             for name, t in self.prog.outputs.items():
                 nb = name.encode()
                 out += struct.pack("<I", len(nb)) + nb
-                out += struct.pack("<IQQQI", self.assign[t.id], 0, t.rows, t.C, 1 if t.dtype == "f32" else 0)
+                out += struct.pack("<IQQQI", self.assign[t.id], 0, t.rows, t.C, {"f32": 1, "i32": 2}.get(t.dtype, 0))
             return out
 
         head = build([0] * len(consts), [0] * len(hosts))

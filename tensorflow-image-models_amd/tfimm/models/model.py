@@ -11,7 +11,7 @@ libtfimm_hip.so.  Subclasses provide
   * ``lower(b, H, W, features)``: trace the forward pass into a layer program.
 """
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -27,6 +27,11 @@ class WeightSpec:
     shape: Tuple[int, ...]
     kind: str          # conv | dwconv | dense | bias | gamma | beta | mean | var | token | pos | table | scale
     init: str = ""     # keras-default initialiser override: "zeros" | "ones" | ""
+
+
+#: what ``Model.top_k`` returns: three ``Tensor`` of shape (B, k) -- int32 class indices, float32 logits, float32 softmax
+#: probabilities -- ordered by value descending, equal values by ascending class (``tf.math.top_k``)
+TopK = namedtuple("TopK", ["indices", "values", "probs"])
 
 
 class Tensor:
@@ -48,6 +53,8 @@ class Tensor:
         return self._t
 
     def numpy(self) -> np.ndarray:
+        if not self._t.dtype.is_floating_point:
+            return self._t.cpu().numpy()                     # class indices stay int32
         return self._t.float().cpu().numpy()
 
     def __array__(self, dtype=None, copy=None):
@@ -244,16 +251,46 @@ class Model:
         return int(sum(int(np.prod(s.shape)) for s in self._specs.values()))
 
     # -- program cache -------------------------------------------------------------------------
-    def program(self, H: Optional[int] = None, W: Optional[int] = None, want_features=False) -> Program:
+    def program(self, H: Optional[int] = None, W: Optional[int] = None, want_features=False,
+                top_k: Optional[int] = None) -> Program:
+        """``top_k``: the program ends in one more op behind its logits (engine/graph.py Builder.topk) and has the outputs
+        ``topk_values`` / ``topk_indices`` / ``topk_probs`` next to them -- a program of its own under a key of its own;
+        without it keys and programs are what they were."""
         H = H or self.cfg.input_size[0]
         W = W or self.cfg.input_size[1]
-        key = (H, W, bool(want_features), precision.get())
+        key = (H, W, bool(want_features), precision.get()) + self._topk_key(top_k)
         if key not in self._programs:
+            if top_k:
+                self._check_top_k(top_k)
             b = Builder(self._weights)
             b.p.const_cache = self._const_cache
             self.lower(b, H, W, want_features)
+            if top_k:
+                logits = b.p.outputs["logits"]
+                # a tensor of several heads side by side (distilled DeiT: 2 x nb_classes columns): top-k per head
+                b.topk(logits, top_k, heads=max(1, logits.C // self.cfg.nb_classes))
             self._programs[key] = b.finish()
         return self._programs[key]
+
+    @staticmethod
+    def _topk_key(top_k: Optional[int]) -> tuple:
+        """the element ``top_k`` adds to the keys of programs, plans and recordings; nothing when it is not set"""
+        return (("topk", int(top_k)),) if top_k else ()
+
+    def _check_top_k(self, k) -> None:
+        """``ValueError`` for what tfimm_hip_topk would refuse, before any device work"""
+        from ..engine import ffi
+        n = int(self.cfg.nb_classes)
+        if n == 0:
+            raise ValueError(f"{self.name}: top_k needs a classifier, this model has nb_classes == 0")
+        if n > ffi.TOPK_MAX_N:
+            raise ValueError(f"{self.name}: top_k holds a row of logits in LDS: nb_classes = {n} exceeds the limit "
+                             f"TFIMM_TOPK_MAX_N = {ffi.TOPK_MAX_N}")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"{self.name}: top_k: k must be an integer, got {k!r}")
+        if k < 1 or k > n or k > ffi.TOPK_MAX_K:
+            raise ValueError(f"{self.name}: top_k: k = {k}, must be in [1, min(nb_classes = {n}, TFIMM_TOPK_MAX_K = "
+                             f"{ffi.TOPK_MAX_K})]")
 
     # -- forward ---------------------------------------------------------------------------------
     @property
@@ -295,12 +332,12 @@ class Model:
             raise RuntimeError("tfimm (MI355X engine) needs a ROCm GPU: no CPU execution path exists.")
         return x.to("cuda", non_blocking=True).contiguous()
 
-    def _run(self, x, want_features: bool):
+    def _run(self, x, want_features: bool, top_k: Optional[int] = None):
         import torch
         xd = self._to_device(x)
         norm = (tuple(x.mean), tuple(x.std)) if isinstance(x, DeferredInput) else None
         if isinstance(xd, list):
-            return self._run_mixed(xd, norm, x.resize, want_features)
+            return self._run_mixed(xd, norm, x.resize, want_features, top_k)
         B, H, W, _ = xd.shape
         src = ()
         if norm is not None and x.resize is not None:
@@ -311,7 +348,8 @@ class Model:
             aa = len(x.resize) > 3
             norm = norm + ((method, crop_pct) + ((True,) if aa else ()),)
             src = (("src",) + tuple(xd.shape[1:3]) + (("antialias",) if aa else ()),)
-        prog = self.program(H, W, want_features)
+        prog = self.program(H, W, want_features, top_k)
+        src = src + self._topk_key(top_k)
         mb = self.micro_batch or B
         mb = min(mb, B)
         if self.branches > 1 and mb == B and B >= 2 * self.branches and prog.supports_branches():
@@ -353,7 +391,7 @@ class Model:
             out[name] = v
         return out
 
-    def _run_mixed(self, imgs, norm, resize, want_features: bool):
+    def _run_mixed(self, imgs, norm, resize, want_features: bool, top_k: Optional[int] = None):
         """A list of uint8 images, each of a size of its own.  The program is the one of the model's input
         size; the keys carry ``("src", "mixed")`` in place of a source size, so every mix of sizes meets the same plan and the
         same recording.  Per chunk: the plan builds records and tables on the host and uploads them with the packed pixels
@@ -365,8 +403,8 @@ class Model:
         method, crop_pct, (H, W) = resize[:3]
         aa = len(resize) > 3
         norm = norm + ((method, crop_pct) + ((True,) if aa else ()),)
-        src = (("src", "mixed") + (("antialias",) if aa else ()),)
-        prog = self.program(H, W, want_features)
+        src = (("src", "mixed") + (("antialias",) if aa else ()),) + self._topk_key(top_k)
+        prog = self.program(H, W, want_features, top_k)
         B = len(imgs)
         mb = min(self.micro_batch or B, B)
         results: Dict[str, list] = {k: [] for k in prog.outputs}
@@ -455,6 +493,19 @@ class Model:
             raise NotImplementedError("This engine implements the inference forward path only (training=False).")
         out = self._run(x, return_features)
         return self._finish(out, "logits", return_features)
+
+    def top_k(self, x, k: int = 5, training: bool = False) -> TopK:
+        """Which classes, how sure: ``TopK(indices, values, probs)`` of ``model(x)`` -- each (B, k): int32 class indices,
+        the float32 logits at them and their softmax probabilities over all classes -- by value descending, equal values by
+        ascending class (``tf.nn.softmax`` + ``tf.math.top_k`` behind ``model(x)`` in a caller of the reference).  Takes
+        everything ``__call__`` takes; the selection is the last launch of the same program (tfimm_hip_topk), from the
+        second call on the last node of the same recording, so only ``3 * B * k`` numbers leave the device.  A model whose
+        logits hold several heads (distilled DeiT: (B, 2, nb_classes)) answers per head: (B, 2, k)."""
+        if training:
+            raise NotImplementedError("This engine implements the inference forward path only (training=False).")
+        self._check_top_k(k)
+        out = self._run(x, False, top_k=int(k))
+        return TopK(Tensor(out["topk_indices"]), Tensor(out["topk_values"]), Tensor(out["topk_probs"]))
 
     def forward_features(self, x, training: bool = False, return_features: bool = False):
         if training:
