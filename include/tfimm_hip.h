@@ -817,6 +817,45 @@ TFIMM_API int tfimm_hip_topk(const float* logits, int64_t ld, int B, int N, int 
                              float* probs, void* stream);
 
 /* =======================================================================================
+ * EMBEDDING END (csrc/embed.hip): row normalisation of float32 embeddings, and the search of a bf16 gallery
+ * ======================================================================================= */
+
+/* tfimm_hip_l2_normalize: y[b][:] = x[b][:] * (1 / sqrt(max(sum_e x[b][e]^2, 1e-12))) for B rows of E float32 values
+ * (tf.math.l2_normalize, axis = -1); x [B][ld_x], y [B][ld_y], ld >= E; y may be x.
+ * One wave per row: per-lane partial sums over columns lane, lane + 64, ... in ascending order, a fixed six-step butterfly,
+ * correctly rounded square root and division.  No atomics, no allocation, capturable; bit-reproducible, a row's result does
+ * not depend on B.  TFIMM_EINVAL before any launch for null x / y, E < 1, ld_x < E, ld_y < E, B < 0; B == 0 launches nothing.
+ * Float32 under every precision mode: no tfimm_hip_ref_* twin. */
+TFIMM_API int tfimm_hip_l2_normalize(const float* x, int64_t ld_x, int B, int E, float* y, int64_t ld_y, void* stream);
+
+/* tfimm_hip_embed_search: for each of B float32 queries q [B][ld_q] the k rows of the bf16 gallery g [N][ld_g] with the largest
+ * inner product.  The queries are rounded to bf16 (nearest even), score[b][n] = sum_e q16[b][e] * g[n][e] accumulated in
+ * float32 by the matrix unit.
+ *   scores  float32 [B][k]   the selected scores
+ *   indices int32   [B][k]   their gallery rows
+ * Order: score descending, equal scores by ascending gallery row (the order of tfimm_hip_topk).  Specified for finite
+ * inputs; others do not fault.  tests/embed_ref.py restates the rule on the CPU.
+ * Two launches on `stream`: pass 1 scores `chunk` gallery rows per workgroup against 32 queries and leaves k candidates per
+ * (query, chunk) in `workspace`; pass 2 selects k of them per query.  The B x N score matrix never exists.  chunk == 0: the
+ * library chooses; otherwise a positive multiple of 32 with ceil(N / chunk) * k <= 16384.  The result does not depend on
+ * chunk, on B, or on which queries share a call: bit-reproducible, no atomics, no scratch memory, capturable.
+ * Limits: E a multiple of 16 in [TFIMM_EMBED_MIN_E, TFIMM_EMBED_MAX_E]; 1 <= k <= min(N, TFIMM_EMBED_MAX_K); 1 <= N < 2^31;
+ * 0 <= B <= TFIMM_EMBED_MAX_B (query tiles of 32 are one grid dimension);
+ * ld_q >= E; ld_g >= E and a multiple of 8 elements; g 16-byte aligned, q / scores / indices / workspace 4-byte aligned;
+ * workspace_bytes >= tfimm_hip_embed_search_workspace(B, N, E, k, chunk); offsets are 64-bit.  Everything else is
+ * TFIMM_EINVAL before any launch, with a message naming the argument.  B == 0 returns 0 and launches nothing.
+ * tfimm_hip_embed_search_workspace returns the bytes of workspace a call with these arguments needs (TFIMM_EINVAL, negative,
+ * for arguments the search would refuse).
+ * Replaces, behind an embedding model: tf.matmul(emb, gallery, transpose_b=True) + tf.math.top_k. */
+#define TFIMM_EMBED_MIN_E 16
+#define TFIMM_EMBED_MAX_E 2048
+#define TFIMM_EMBED_MAX_K 64
+#define TFIMM_EMBED_MAX_B 2097120 /* 65535 * 32 */
+TFIMM_API int64_t tfimm_hip_embed_search_workspace(int B, int N, int E, int k, int chunk);
+TFIMM_API int tfimm_hip_embed_search(const float* q, int64_t ld_q, int B, const void* g, int64_t ld_g, int N, int E, int k, int chunk,
+                                     float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* =======================================================================================
  * FLOAT32 VERIFICATION PATH (csrc/ref32.hip; selected by TFIMM_PRECISION=fp32, tfimm/engine/precision.py)
  *
  * The reference is float32 end to end and pins values at 1e-3 relative to the maximum (tests/test_timm.py:71).  The

@@ -23,28 +23,11 @@
 //
 // LDS traffic: the scans read lds[tid + 256 i] (consecutive lanes, consecutive banks: conflict-free); the stores behind a
 // 16-byte load hit every fourth bank (4-way on ds_write_b32: twice its conflict-free time, once per row).
-#include "common.h"
-
-#include <climits>
+#include "topk_select.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kKeyNaN = 0xffffffffu;    // every NaN
-constexpr uint32_t kKeyZero = 0x80000000u;   // +0.0 and -0.0
-constexpr uint32_t kRetired = 0u;            // below key(-inf) = 0x007fffff
-
-__device__ __forceinline__ uint32_t key_of(uint32_t b) {
-  if ((b & 0x7fffffffu) > 0x7f800000u) return kKeyNaN;
-  if (b == 0x80000000u) b = 0u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-// the float a key stands for; +0.0 for both zeros, one quiet NaN for every NaN
-__device__ __forceinline__ uint32_t bits_of(uint32_t key) { return (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key; }
-
-// (key, column) order of the selection: larger key first, of equal keys the lower column
-__device__ __forceinline__ bool beats(uint32_t ka, int ia, uint32_t kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
+using namespace topk_sel;   // key_of / bits_of / beats / select_round: shared with embed.hip
 
 struct TopkArgs {
   const uint32_t* logits;   // float32 bits
@@ -79,28 +62,10 @@ __global__ void __launch_bounds__(kThreads) topk_kernel(TopkArgs a) {
 
   float m = 0.f, sum = 1.f;
   for (int j = 0; j < a.k; ++j) {
-    // ---- this thread's best: ascending columns, strict comparison
-    uint32_t bk = kRetired;
-    int bi = INT_MAX;
-    for (int c = tid; c < N; c += kThreads) {
-      const uint32_t q = keys[c];
-      if (q > bk) { bk = q; bi = c; }
-    }
-    // ---- the wave's best in every lane
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint32_t ok = __shfl_xor(bk, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (beats(ok, oi, bk, bi)) { bk = ok; bi = oi; }
-    }
-    if (lane == 0) { w_key[wave] = bk; w_idx[wave] = bi; }
-    __syncthreads();
-    // ---- the workgroup's best in every thread: (w0, w1), (w2, w3), then the two
-    uint32_t k0 = w_key[0], k1 = w_key[2];
-    int i0 = w_idx[0], i1 = w_idx[2];
-    if (beats(w_key[1], w_idx[1], k0, i0)) { k0 = w_key[1]; i0 = w_idx[1]; }
-    if (beats(w_key[3], w_idx[3], k1, i1)) { k1 = w_key[3]; i1 = w_idx[3]; }
-    if (beats(k1, i1, k0, i0)) { k0 = k1; i0 = i1; }
+    // ---- the workgroup's best (key, column) in every thread (topk_select.h)
+    uint32_t k0;
+    int i0;
+    select_round(keys, N, tid, w_key, w_idx, k0, i0);
 
     if (j == 0 && a.probs != nullptr) {
       // ---- row maximum = this winner; sum of exp(x - max) over the LDS copy, nothing retired yet

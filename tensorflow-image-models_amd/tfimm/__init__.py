@@ -5,7 +5,9 @@ Drop-in for the inference path of martinsbruveris/tensorflow-image-models:
 (reference tfimm/__init__.py:1-12).  Importing the package registers all architectures.
 """
 from . import architectures, layers  # noqa: F401
+from .models.embedding_model import EmbeddingModel  # noqa: F401
 from .models.factory import create_model, create_preprocessing  # noqa: F401
+from .models.gallery import Gallery, Matches  # noqa: F401
 from .models.model import Tensor, TopK  # noqa: F401
 from .models.registry import list_models  # noqa: F401
 from .utils import (  # noqa: F401

@@ -220,6 +220,11 @@ SYMBOLS = {
     "tfimm_hip_bias_act": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     # the output end (csrc/topk.hip): logits, ld, B, N, k, values, indices, probs
     "tfimm_hip_topk": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # the embedding end (csrc/embed.hip): x, ld_x, B, E, y, ld_y | B, N, E, k, chunk |
+    # q, ld_q, B, g, ld_g, N, E, k, chunk, scores, indices, workspace, workspace_bytes
+    "tfimm_hip_l2_normalize": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
+    "tfimm_hip_embed_search_workspace": (_i64, [_i, _i, _i, _i, _i]),
+    "tfimm_hip_embed_search": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     # program-level entry points (csrc/plan.hip): a serialised plan (graph.Plan.export) run without Python host logic
     "tfimm_hip_plan_query": (_i, [_vp, C.c_size_t, _vp]),
     "tfimm_hip_plan_create": (_i, [_vp, C.c_size_t, _vp, _vp, C.POINTER(_vp)]),
@@ -335,6 +340,10 @@ RESIZE_AA_TILE_ROWS, RESIZE_AA_TILE_COLS, RESIZE_AA_MAX_BLOCKS = 16, 32, 1024
 
 # include/tfimm_hip.h: the domain of tfimm_hip_topk (k selection rounds over a row held in LDS)
 TOPK_MAX_K, TOPK_MAX_N = 64, 32768
+
+# include/tfimm_hip.h: the domain of tfimm_hip_embed_search (E a multiple of 16; the gallery row pitch a multiple of 8 elements)
+EMBED_MIN_E, EMBED_MAX_E, EMBED_MAX_K = 16, 2048, 64
+EMBED_MAX_B = 65535 * 32          # queries per call: tiles of 32 are one grid dimension
 
 
 def resize_span_taps(n_in: int, n_resized: int, method: str) -> int:

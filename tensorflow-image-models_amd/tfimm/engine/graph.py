@@ -1135,6 +1135,15 @@ class Builder:
             p.mark_output("topk_probs", pr)
         return values, indices, pr
 
+    def l2_normalize(self, x: TRef, cite="tf.math.l2_normalize(x, axis=-1)", name="") -> TRef:
+        """``y = x * (1 / sqrt(max(sum(x^2), 1e-12)))`` over the last axis of a float32 tensor, float32 out
+        (tfimm_hip_l2_normalize: one wave per row; the same kernel under every precision mode)."""
+        if x.dtype != "f32":
+            raise ValueError(f"l2_normalize reads a float32 tensor, got {x.dtype}")
+        out = self.p.new_tensor(x.rows, x.C, x.H, x.W, dtype="f32", name=name or "l2_normalize")
+        self.p.add("l2_normalize", [x], out, cite=cite, rows=x.rows, E=x.C)
+        return out
+
     def reshape(self, x: TRef, rows: int, C: int, H=0, W=0) -> TRef:
         """Free reinterpretation of a contiguous tensor (tf.reshape)."""
         assert rows * C == x.rows * x.C
@@ -1495,11 +1504,15 @@ class Plan:
                 self.calls.append((lib.tfimm_hip_topk,
                                    (self.tptr(op.inputs[0]), a["ld"], B * a["rows"], a["N"], a["k"], self.tptr(op.output),
                                     self.tptr(op.extra_outputs[0]), pr)))
+            elif k == "l2_normalize":
+                # float32 on both sides under every precision: the same kernel on all three paths (_FP32_SHARED)
+                self.calls.append((lib.tfimm_hip_l2_normalize,
+                                   (self.tptr(op.inputs[0]), a["E"], B * a["rows"], a["E"], self.tptr(op.output), a["E"])))
             else:
                 raise NotImplementedError(k)
 
     # kernels that are float32 on both paths
-    _FP32_SHARED = ("tfimm_hip_se_gate", "tfimm_hip_eca_gate", "tfimm_hip_topk")
+    _FP32_SHARED = ("tfimm_hip_se_gate", "tfimm_hip_eca_gate", "tfimm_hip_topk", "tfimm_hip_l2_normalize")
 
     def _bind_fp32(self):
         """Verification path (engine/precision.py): every call of the list goes to the float32 kernel of the same name
@@ -1644,6 +1657,10 @@ class Plan:
         if self._resize_tabs or self._mixed:
             raise NotImplementedError("plans run with a resize spec are not exported: tfimm_hip_plan_forward takes float32 / "
                                       "bf16 images of the program's input size only")
+        if any(op.kind == "l2_normalize" for op in self.prog.ops):
+            # the executor's call table (csrc/plan.hip) has no entry for it: refuse, never emit a blob that skips the op
+            raise NotImplementedError("plans that hold the op l2_normalize (tfimm_hip_l2_normalize; EmbeddingModel(..., "
+                                      "normalize=True)) are not exported")
         if self.device == "cpu":
             raise RuntimeError("export needs a plan built on the GPU (tile hints and occupancy are resolved there)")
         consts = self.prog._dev_consts
