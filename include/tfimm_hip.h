@@ -816,6 +816,53 @@ TFIMM_API int tfimm_hip_gemm_mx(const tfimm_gemm_mx_desc* d, void* stream);
 TFIMM_API int tfimm_hip_topk(const float* logits, int64_t ld, int B, int N, int k, float* values, int32_t* indices,
                              float* probs, void* stream);
 
+/* tfimm_hip_score: per row of logits [B][ld] (float32, N <= ld valid columns) and its label labels[b], each [B]:
+ *   loss  float32  log(sum_i exp(x_i - m)) - (x_y - m), m the row maximum: tf.nn.sparse_softmax_cross_entropy_with_logits.
+ *                  sum >= 1 (the maximum's own term is exp(0)), so loss >= +0, and loss == 0 exactly for N == 1.  Specified
+ *                  for rows whose entries are all finite; other rows get whatever float this arithmetic gives.
+ *   rank  int32    the number of columns that beat column y in the order of tfimm_hip_topk (a larger value, or an equal value
+ *                  in a lower column; NaN above +inf, -0.0 == +0.0): rank < k exactly when y is in tfimm_hip_topk(..., k)'s
+ *                  indices, at position rank.  tf.math.in_top_k counts every tie with the k-th value as a hit; this follows
+ *                  tf.math.top_k instead, so that the library's two answers agree: in an all-equal row only class 0 has rank 0.
+ *   pred  int32    the first maximum (tf.argmax); indices[b][0] of tfimm_hip_topk
+ *   prob  float32  exp(x_y - m) / sum: the arithmetic of tfimm_hip_topk, bit-equal to its probs[b][rank] whenever rank < k
+ * Labels: y == TFIMM_SCORE_IGNORE (the padded tail of a dataset's last batch) is not scored: loss = 0, prob = 0, rank = -1;
+ * y < -1 or y >= N likewise with rank = -2.  pred is written for every row.  No column outside [0, N) is read whatever the
+ * label holds.  tests/score_ref.py restates the rule on the CPU.
+ * Accumulators, each updated by the same launch when its pointer is not NULL, with 64- / 32-bit INTEGER atomic adds issued by
+ * one thread per row -- integer adds commute, so the contents after any sequence of launches are bit-identical whatever the
+ * split into batches, the order of the rows, or the scheduling.  The caller zeroes them.
+ *   state      int64 [TFIMM_SCORE_STATE_WORDS]:
+ *                [TFIMM_SCORE_SCORED]  rows with a label in [0, N)     [TFIMM_SCORE_IGNORED]  rows with label -1
+ *                [TFIMM_SCORE_INVALID] rows with any other label       [TFIMM_SCORE_LOSS_EXCLUDED]  scored rows for which
+ *                loss < 1024.0f is false (NaN, inf, absurd): left out of the loss sum, their rank still counts
+ *                [TFIMM_SCORE_LOSS_Q]  sum of rint((double)loss * 2^32) over the other scored rows: at most 2^42 units per
+ *                row, so the int64 sum cannot overflow within 2^21 rows at that cap (at a loss of 16 per row: 2^27 rows)
+ *                [TFIMM_SCORE_RANK_HIST + r]  rows with rank == r < 64; [TFIMM_SCORE_RANK_HIST + 64] every higher rank
+ *   per_class  int64 [2][N]: [0][y] += 1, [1][y] += (rank == 0), over scored rows
+ *   confusion  uint32 [N][N]: [y][pred] += 1 over scored rows; N <= TFIMM_SCORE_MAX_CONFUSION_N (64 MB)
+ * One workgroup of 256 threads per row, the row read once and kept in LDS (the loader, the keys and the sum of
+ * tfimm_hip_topk: csrc/topk_row.h), hence N <= TFIMM_SCORE_MAX_N; one selection round, then one pass over LDS for the sum and
+ * the rank.  No allocation, capturable; a row's four outputs do not depend on B.  TFIMM_EINVAL before any launch, naming the
+ * argument: NULL logits / labels / loss / rank / pred / prob; a pointer that is not 4-byte (state, per_class: 8-byte)
+ * aligned; N outside [1, TFIMM_SCORE_MAX_N]; ld < N; B < 0; confusion with N > TFIMM_SCORE_MAX_CONFUSION_N.  B == 0 returns 0
+ * and launches nothing.  Float32 logits under every precision mode: no tfimm_hip_ref_* twin.
+ * Replaces, in a caller of the reference (tfimm/train/problems/classification.py): logits to the host, softmax_loss and
+ * tf.argmax there. */
+#define TFIMM_SCORE_MAX_N TFIMM_TOPK_MAX_N
+#define TFIMM_SCORE_MAX_CONFUSION_N 4096
+#define TFIMM_SCORE_IGNORE (-1)
+#define TFIMM_SCORE_SCORED 0
+#define TFIMM_SCORE_IGNORED 1
+#define TFIMM_SCORE_INVALID 2
+#define TFIMM_SCORE_LOSS_EXCLUDED 3
+#define TFIMM_SCORE_LOSS_Q 4
+#define TFIMM_SCORE_RANK_HIST 5
+#define TFIMM_SCORE_RANK_BINS 65
+#define TFIMM_SCORE_STATE_WORDS 70
+TFIMM_API int tfimm_hip_score(const float* logits, int64_t ld, int B, int N, const int32_t* labels, float* loss, int32_t* rank,
+                              int32_t* pred, float* prob, int64_t* state, int64_t* per_class, uint32_t* confusion, void* stream);
+
 /* =======================================================================================
  * EMBEDDING END (csrc/embed.hip): row normalisation of float32 embeddings, and the search of a bf16 gallery
  * ======================================================================================= */

@@ -23,11 +23,11 @@
 //
 // LDS traffic: the scans read lds[tid + 256 i] (consecutive lanes, consecutive banks: conflict-free); the stores behind a
 // 16-byte load hit every fourth bank (4-way on ds_write_b32: twice its conflict-free time, once per row).
-#include "topk_select.h"
+#include "topk_row.h"
 
 namespace {
 
-using namespace topk_sel;   // key_of / bits_of / beats / select_round: shared with embed.hip
+using namespace topk_sel;   // key_of / bits_of / beats / select_round: shared with embed.hip; the row passes with score.hip
 
 struct TopkArgs {
   const uint32_t* logits;   // float32 bits
@@ -43,21 +43,12 @@ __global__ void __launch_bounds__(kThreads) topk_kernel(TopkArgs a) {
   __shared__ uint32_t w_key[kWaves];
   __shared__ int w_idx[kWaves];
   __shared__ float w_sum[kWaves];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int N = a.N;
   const uint32_t* row = a.logits + (int64_t)blockIdx.x * a.ld;
 
-  // ---- the row -> keys in LDS: scalar head up to the first 16-byte boundary, 16-byte body, scalar tail
-  const int head = min(N, (int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 2));
-  const int nvec = (N - head) >> 2;
-  for (int c = tid; c < head; c += kThreads) keys[c] = key_of(row[c]);
-  const uint4* body = reinterpret_cast<const uint4*>(row + head);
-  for (int v = tid; v < nvec; v += kThreads) {
-    const uint4 u = body[v];
-    uint32_t* dst = keys + head + 4 * v;
-    dst[0] = key_of(u.x); dst[1] = key_of(u.y); dst[2] = key_of(u.z); dst[3] = key_of(u.w);
-  }
-  for (int c = head + 4 * nvec + tid; c < N; c += kThreads) keys[c] = key_of(row[c]);
+  // ---- the row -> keys in LDS: scalar head up to the first 16-byte boundary, 16-byte body, scalar tail (topk_row.h)
+  load_row_keys(row, N, tid, keys);
   __syncthreads();
 
   float m = 0.f, sum = 1.f;
@@ -70,12 +61,7 @@ __global__ void __launch_bounds__(kThreads) topk_kernel(TopkArgs a) {
     if (j == 0 && a.probs != nullptr) {
       // ---- row maximum = this winner; sum of exp(x - max) over the LDS copy, nothing retired yet
       m = __uint_as_float(bits_of(k0));
-      float s = 0.f;
-      for (int c = tid; c < N; c += kThreads) s += expf(__uint_as_float(bits_of(keys[c])) - m);
-      s = wave_sum(s);
-      if (lane == 0) w_sum[wave] = s;
-      __syncthreads();
-      sum = (w_sum[0] + w_sum[1]) + (w_sum[2] + w_sum[3]);
+      sum = block_sum(sum_exp_partial(keys, N, tid, m, [](uint32_t, int) {}), tid, w_sum);
     }
 
     if (tid == 0 && i0 < N) {       // (k <= N: a round always has a winner; the test keeps a broken invariant inside the row)

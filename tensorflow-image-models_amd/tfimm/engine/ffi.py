@@ -220,6 +220,8 @@ SYMBOLS = {
     "tfimm_hip_bias_act": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     # the output end (csrc/topk.hip): logits, ld, B, N, k, values, indices, probs
     "tfimm_hip_topk": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # the scoring end (csrc/score.hip): logits, ld, B, N, labels, loss, rank, pred, prob, state, per_class, confusion
+    "tfimm_hip_score": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # the embedding end (csrc/embed.hip): x, ld_x, B, E, y, ld_y | B, N, E, k, chunk |
     # q, ld_q, B, g, ld_g, N, E, k, chunk, scores, indices, workspace, workspace_bytes
     "tfimm_hip_l2_normalize": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
@@ -340,6 +342,12 @@ RESIZE_AA_TILE_ROWS, RESIZE_AA_TILE_COLS, RESIZE_AA_MAX_BLOCKS = 16, 32, 1024
 
 # include/tfimm_hip.h: the domain of tfimm_hip_topk (k selection rounds over a row held in LDS)
 TOPK_MAX_K, TOPK_MAX_N = 64, 32768
+
+# include/tfimm_hip.h: the domain of tfimm_hip_score (a row held in LDS; a confusion matrix of at most 64 MB), the label of a row
+# that is not scored, and the layout of the meter state (int64 words)
+SCORE_MAX_N, SCORE_MAX_CONFUSION_N, SCORE_IGNORE = TOPK_MAX_N, 4096, -1
+SCORE_SCORED, SCORE_IGNORED, SCORE_INVALID, SCORE_LOSS_EXCLUDED, SCORE_LOSS_Q, SCORE_RANK_HIST = 0, 1, 2, 3, 4, 5
+SCORE_RANK_BINS, SCORE_STATE_WORDS = 65, 70
 
 # include/tfimm_hip.h: the domain of tfimm_hip_embed_search (E a multiple of 16; the gallery row pitch a multiple of 8 elements)
 EMBED_MIN_E, EMBED_MAX_E, EMBED_MAX_K = 16, 2048, 64

@@ -158,6 +158,9 @@ class EmbeddingModel(Model):
     def top_k(self, x, k: int = 5, training: bool = False):
         raise ValueError(f"{self.name}: top_k needs a classifier, an embedding model has none (search a Gallery instead)")
 
+    def evaluate(self, x, labels, meter=None, training: bool = False):
+        raise ValueError(f"{self.name}: evaluate needs a classifier, an embedding model has none (search a Gallery instead)")
+
     def search(self, x, gallery, k: int = 5):
         """``gallery.search(model(x), k)``: the model's recording, then the two launches of the search, on the same stream;
         ``Matches(indices, scores)``, each (B, k).  The embeddings never leave the device."""

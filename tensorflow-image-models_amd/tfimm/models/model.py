@@ -507,6 +507,39 @@ class Model:
         out = self._run(x, False, top_k=int(k))
         return TopK(Tensor(out["topk_indices"]), Tensor(out["topk_values"]), Tensor(out["topk_probs"]))
 
+    def _check_evaluate(self, x, labels, meter):
+        """``ValueError`` for what ``evaluate`` cannot score, before any device work; returns the checked labels as the
+        callable that uploads them"""
+        from ..engine import ffi
+        n = int(self.cfg.nb_classes)
+        if n == 0:
+            raise ValueError(f"{self.name}: evaluate needs a classifier, this model has nb_classes == 0")
+        if n > ffi.SCORE_MAX_N:
+            raise ValueError(f"{self.name}: evaluate holds a row of logits in LDS: nb_classes = {n} exceeds the limit "
+                             f"TFIMM_SCORE_MAX_N = {ffi.SCORE_MAX_N}")
+        heads = self.program().outputs["logits"].C // n          # (lowering is host work)
+        if heads != 1:
+            raise ValueError(f"{self.name}: the logits hold {heads} heads per image; evaluate scores one (score a head's "
+                             f"logits with tfimm.score)")
+        if meter is not None and meter.nb_classes != n:
+            raise ValueError(f"{self.name}: the meter counts {meter.nb_classes} classes, the model has nb_classes = {n}")
+        from .meter import _labels
+        batch = len(x.data) if isinstance(x, DeferredInput) and x.mixed else len(x) if isinstance(x, (list, tuple)) else x.shape[0]
+        return _labels(labels, int(batch), f"{self.name}: evaluate")
+
+    def evaluate(self, x, labels, meter=None, training: bool = False):
+        """How good on labelled data: ``tfimm.score(model(x), labels, meter)`` -- ``Scores(loss, rank, pred, prob)``, each
+        (B,): the softmax cross-entropy, the rank of the true class among the logits, the predicted class and the true class's
+        probability; with a ``tfimm.Meter`` the batch is added to its running accuracy@k and mean loss on the device.  Takes
+        everything ``__call__`` takes.  The scoring launch (tfimm_hip_score) runs behind the model's program or recording on
+        the same stream -- it is not part of them, labels being a second per-call input -- so the logits never leave the
+        device and no program, plan or recording is added.  A label of -1 marks a padded row that is not scored."""
+        if training:
+            raise NotImplementedError("This engine implements the inference forward path only (training=False).")
+        from .meter import _score
+        labels = self._check_evaluate(x, labels, meter)
+        return _score(self(x), labels, meter, f"{self.name}: evaluate")
+
     def forward_features(self, x, training: bool = False, return_features: bool = False):
         if training:
             raise NotImplementedError("This engine implements the inference forward path only (training=False).")
