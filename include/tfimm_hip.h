@@ -903,6 +903,41 @@ TFIMM_API int tfimm_hip_embed_search(const float* q, int64_t ld_q, int B, const 
                                      float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* =======================================================================================
+ * LOW-RANK ADAPTER (csrc/lora.hip): the LoRA term of a Dense layer as an op of its own
+ * ======================================================================================= */
+
+/* tfimm_hip_lora_delta:
+ *     t   = bf16( x[M][K] . A[K][R] )                      fp32 accumulation, ONE rounding of t
+ *     out = bf16( residual[M][N] + t[M][R] . B'[R][N] )    fp32 accumulation, residual optional
+ * in ONE launch; t lives in registers only (the accumulators of the first product are the matrix unit's operand of the
+ * second).  The unmerged form of LoRADense.call (reference architectures/lora/layers.py:81-113): the caller folds
+ * scaling = lora_alpha / lora_rank (and a LayerScale behind the layer) into B' and hands `out` to tfimm_hip_gemm as the
+ * residual of the layer's full-rank product, so the adapter's weights stay apart from the layer's.
+ *   x        bf16 [M][lda]
+ *   a        bf16 [Rp][lda_a]   A transposed; rows >= the true rank are zero.  Rp a multiple of 16, 16 <= Rp <= TFIMM_LORA_MAX_RP
+ *   b        bf16 [N][Rp]       B' transposed; columns >= the true rank are zero
+ *   residual bf16 [M][ldr] or NULL
+ *   out      bf16 [M][ldc]
+ * Limits: K % 8 == 0, N % 8 == 0, 8 <= K, N <= TFIMM_LORA_MAX_DIM (TFIMM_EUNSUP otherwise, and for an Rp outside its set).
+ * TFIMM_EINVAL: a null x / a / b / out, M < 0, a pitch below its row or not a multiple of 8 elements, a pointer that is not
+ * 16-byte aligned, `out` overlapping any input.  No launch is made in either case; M == 0 returns 0 and launches nothing.
+ * A row's result does not depend on M: no atomics, no workspace, capturable, bit-reproducible.  Offsets are 64-bit.
+ * tests/lora_ref.py restates the contract in float64. */
+#define TFIMM_LORA_MAX_RP 64
+#define TFIMM_LORA_MAX_DIM 8192
+typedef struct tfimm_lora_desc {
+  const void* x;
+  const void* a;
+  const void* b;
+  const void* residual;
+  void* out;
+  int64_t M;
+  int32_t K, N, Rp;
+  int32_t lda, lda_a, ldr, ldc;
+} tfimm_lora_desc;
+TFIMM_API int tfimm_hip_lora_delta(const tfimm_lora_desc* d, void* stream);
+
+/* =======================================================================================
  * FLOAT32 VERIFICATION PATH (csrc/ref32.hip; selected by TFIMM_PRECISION=fp32, tfimm/engine/precision.py)
  *
  * The reference is float32 end to end and pins values at 1e-3 relative to the maximum (tests/test_timm.py:71).  The
@@ -954,6 +989,9 @@ TFIMM_API int tfimm_hip_ref_attention_probs(const void* qkv, void* probs, int B,
 TFIMM_API int tfimm_hip_ref_talking_heads_attention(const tfimm_tha_desc* d, void* stream);
 TFIMM_API int tfimm_hip_ref_class_attention(const void* q, const void* kv, void* out, int B, int n_tokens, int heads, int hd,
                                             int ldq, int ldkv, int ldo, void* stream);
+/* tfimm_hip_lora_delta on float32 tensors (x, a, b, residual, out all float, same descriptor, 4-byte alignment): t is NOT
+ * rounded.  Same limits and refusals. */
+TFIMM_API int tfimm_hip_ref_lora_delta(const tfimm_lora_desc* d, void* stream);
 
 /* =======================================================================================
  * PROGRAM-LEVEL ENTRY POINTS (csrc/plan.hip): a whole forward behind three calls, for hosts without Python.

@@ -292,4 +292,7 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// descriptor checks shared by tfimm_hip_lora_delta (lora.hip) and its float32 twin (ref32.hip)
+int tfimm_lora_validate(const tfimm_lora_desc* d, int elem_bytes, int align, const char* who);
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

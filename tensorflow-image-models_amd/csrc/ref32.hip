@@ -493,6 +493,34 @@ __global__ void __launch_bounds__(64) ref_class_attn_kernel(const float* q, cons
   }
 }
 
+// ------------------------------------------------------------------------------------------------- LoRA low-rank term
+// out[m][:] = residual[m][:] + (x[m][:] . A) . B' in float32, t unrounded: one workgroup per row (grid-stride); wave w forms
+// the ranks w, w + 4, ... (lanes stride over k, butterfly sum), then every thread forms output columns.
+__global__ void __launch_bounds__(256) ref_lora_delta_kernel(const float* x, const float* a, const float* b, const float* residual,
+                                                             float* out, int64_t M, int K, int N, int Rp, int64_t lda,
+                                                             int64_t lda_a, int64_t ldr, int64_t ldc) {
+  __shared__ float t[TFIMM_LORA_MAX_RP];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t m = blockIdx.x; m < M; m += gridDim.x) {
+    const float* xr = x + m * lda;
+    for (int r = wave; r < Rp; r += 4) {
+      const float* ar = a + r * lda_a;
+      float acc = 0.f;
+      for (int k = lane; k < K; k += 64) acc = fmaf(xr[k], ar[k], acc);
+      acc = wave_sum(acc);
+      if (lane == 0) t[r] = acc;
+    }
+    __syncthreads();
+    for (int n = threadIdx.x; n < N; n += 256) {
+      const float* br = b + (int64_t)n * Rp;
+      float acc = 0.f;
+      for (int r = 0; r < Rp; ++r) acc = fmaf(t[r], br[r], acc);
+      out[m * ldc + n] = residual ? residual[m * ldr + n] + acc : acc;
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 #define REF_LAUNCH(kernel, grid, block, lds, stream, ...) TFIMM_LAUNCH(kernel, dim3(grid), dim3(block), lds, (hipStream_t)stream, __VA_ARGS__)
@@ -689,6 +717,16 @@ int tfimm_hip_ref_class_attention(const void* q, const void* kv, void* out, int 
   if ((size_t)n_tokens * 4 > 64 * 1024) TFIMM_FAIL(TFIMM_EUNSUP, "ref_class_attention: too many tokens");
   REF_LAUNCH(ref_class_attn_kernel, (unsigned)(B * heads), 64, (size_t)n_tokens * 4, stream, (const float*)q, (const float*)kv, (float*)out,
              n_tokens, heads, hd, ldq, ldkv, ldo);
+  return 0;
+}
+
+int tfimm_hip_ref_lora_delta(const tfimm_lora_desc* dp, void* stream) {
+  const int rc = tfimm_lora_validate(dp, 4, 4, "ref_lora_delta");
+  if (rc) return rc;
+  const tfimm_lora_desc& d = *dp;
+  if (d.M == 0) return 0;
+  REF_LAUNCH(ref_lora_delta_kernel, grid_for(d.M, 1), 256, 0, stream, (const float*)d.x, (const float*)d.a, (const float*)d.b,
+             (const float*)d.residual, (float*)d.out, d.M, d.K, d.N, d.Rp, (int64_t)d.lda, (int64_t)d.lda_a, (int64_t)d.ldr, (int64_t)d.ldc);
   return 0;
 }
 

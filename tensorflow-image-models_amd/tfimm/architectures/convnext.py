@@ -120,17 +120,7 @@ class ConvNeXt(Model):
                 if want_features:
                     b.p.mark_output(f"stage_{j}/downsample", x)
             for i in range(nb):
-                p = f"stages/{j}/blocks/{i}/"
-                y, _ = b.dwconv(x, p + "conv_dw/depthwise_kernel", stride=1, padding=3, bias=p + "conv_dw/bias",
-                                cite="convnext.py:224-225")
-                z = b.mlp_fused(y, p + "norm", eps, p + "mlp/fc1", p + "mlp/fc2", act=c.act_layer, residual=x,
-                                out_scale=p + "gamma", cite="convnext.py:226-232, transformers.py:208-214")
-                if z is None:
-                    h = b.ln_dense(y, p + "norm", eps, p + "mlp/fc1/kernel", p + "mlp/fc1/bias", act=c.act_layer,
-                                   cite_ln="convnext.py:226", cite="transformers.py:209-210")
-                    z = b.dense(h, p + "mlp/fc2/kernel", p + "mlp/fc2/bias", out_scale=p + "gamma", residual=x,
-                                cite="transformers.py:212 + convnext.py:228-230")
-                x = z
+                x = self.lower_block(b, x, f"stages/{j}/blocks/{i}/", eps)
                 if want_features:
                     b.p.mark_output(f"stage_{j}/block_{i}", x)
         b.p.mark_output("conv_features", x)
@@ -142,6 +132,20 @@ class ConvNeXt(Model):
         else:
             logits = feat
         b.p.mark_output("logits", logits)
+
+    def lower_block(self, b, x, p: str, eps: float):
+        """One ConvNeXtBlock (convnext.py:222-232) with the variables under prefix ``p``; returns the block's output."""
+        c = self.cfg
+        y, _ = b.dwconv(x, p + "conv_dw/depthwise_kernel", stride=1, padding=3, bias=p + "conv_dw/bias",
+                        cite="convnext.py:224-225")
+        z = b.mlp_fused(y, p + "norm", eps, p + "mlp/fc1", p + "mlp/fc2", act=c.act_layer, residual=x,
+                        out_scale=p + "gamma", cite="convnext.py:226-232, transformers.py:208-214")
+        if z is None:
+            h = b.ln_dense(y, p + "norm", eps, p + "mlp/fc1/kernel", p + "mlp/fc1/bias", act=c.act_layer,
+                           cite_ln="convnext.py:226", cite="transformers.py:209-210")
+            z = b.dense(h, p + "mlp/fc2/kernel", p + "mlp/fc2/bias", out_scale=p + "gamma", residual=x,
+                        cite="transformers.py:212 + convnext.py:228-230")
+        return z
 
     def forward_features(self, x, training: bool = False, return_features: bool = False):
         """Pre-pooling feature map (convnext.py:383-411), NHWC."""

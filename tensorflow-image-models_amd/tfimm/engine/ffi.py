@@ -112,6 +112,13 @@ class GemmMxDesc(C.Structure):
                 ("out_fmt", C.c_int32), ("act", C.c_int32), ("act_after_res", C.c_int32)]
 
 
+class LoraDesc(C.Structure):
+    """tfimm_lora_desc: the low-rank term of a LoRA Dense layer (csrc/lora.hip)"""
+    _fields_ = [("x", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("residual", C.c_void_p), ("out", C.c_void_p),
+                ("M", C.c_int64), ("K", C.c_int32), ("N", C.c_int32), ("Rp", C.c_int32),
+                ("lda", C.c_int32), ("lda_a", C.c_int32), ("ldr", C.c_int32), ("ldc", C.c_int32)]
+
+
 class ResizeDesc(C.Structure):
     """tfimm_resize_desc: resize + centre crop + normalise of a uint8 batch (csrc/resize.hip)"""
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p),
@@ -227,6 +234,8 @@ SYMBOLS = {
     "tfimm_hip_l2_normalize": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
     "tfimm_hip_embed_search_workspace": (_i64, [_i, _i, _i, _i, _i]),
     "tfimm_hip_embed_search": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    # the low-rank adapter term (csrc/lora.hip)
+    "tfimm_hip_lora_delta": (_i, [C.POINTER(LoraDesc), _vp]),
     # program-level entry points (csrc/plan.hip): a serialised plan (graph.Plan.export) run without Python host logic
     "tfimm_hip_plan_query": (_i, [_vp, C.c_size_t, _vp]),
     "tfimm_hip_plan_create": (_i, [_vp, C.c_size_t, _vp, _vp, C.POINTER(_vp)]),
@@ -255,6 +264,7 @@ SYMBOLS = {
     "tfimm_hip_ref_attention_probs": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "tfimm_hip_ref_talking_heads_attention": (_i, [C.POINTER(ThaDesc), _vp]),
     "tfimm_hip_ref_class_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "tfimm_hip_ref_lora_delta": (_i, [C.POINTER(LoraDesc), _vp]),
     "tfimm_hip_memset_async": (_i, [_vp, _i, C.c_size_t, _vp]),
 }
 

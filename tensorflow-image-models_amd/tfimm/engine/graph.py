@@ -600,8 +600,12 @@ class Builder:
               in_cols: Optional[Tuple[int, int]] = None,
               out: Optional[TRef] = None, out_col: int = 0, out_scale: Optional[str] = None,
               residual_row: Optional[int] = None, out_row: Optional[int] = None,
-              ln: Optional[Tuple[str, float, TRef]] = None, mx: bool = True, cite="", name="") -> TRef:
+              ln: Optional[Tuple[str, float, TRef]] = None, mx: bool = True, act_after_res: bool = False,
+              cite="", name="") -> TRef:
         """tf.keras.layers.Dense (+ activation, + residual add).
+
+        ``act_after_res``: the activation is applied to ``x W + b + residual`` instead of in front of the residual add (the
+        epilogue flag of tfimm_hip_gemm; a LoRA Dense layer adds its low-rank term in front of the activation).
 
         fp8 mode (engine/precision.py): a layer ``mx_eligible`` accepts runs as quant_mx + gemm_mx (csrc/mx.hip); ``mx=False``
         keeps a layer in bf16 (classifier-side layers such as pre_logits).
@@ -637,7 +641,7 @@ class Builder:
         else:
             assert in_cols[1] == kin and in_cols[0] + kin <= x.C
         if mx and ln is None and self.mx_eligible(x, kin, kout) and not out_f32 and row_select is None and in_cols is None \
-                and out is None and residual_row is None and out_row is None:
+                and out is None and residual_row is None and out_row is None and not act_after_res:
             return self._dense_mx(x, k, bvec_in, kernel, act=act, residual=residual, cite=cite, name=name)
         if ln is not None:
             assert residual is None and row_select is None and in_cols is None and not out_f32 and out is None
@@ -648,7 +652,7 @@ class Builder:
             k = (k.astype(np.float64) * gam.reshape(kin, 1)).astype(np.float32)
         wt, bvec = pack.pack_dense(k, bvec_in, fp32=self.fp32)
         rows = x.rows
-        attrs = dict(M=rows, N=kout, K=kin, K_true=kin, mode=0, lda=x.C, act=act, act_after_res=False,
+        attrs = dict(M=rows, N=kout, K=kin, K_true=kin, mode=0, lda=x.C, act=act, act_after_res=bool(act_after_res),
                      out_f32=1 if out_f32 else 0, res_mod=0, remap=None, ldw=wt.shape[1],
                      a_rows_per_image=x.rows)
         if row_select is not None:
@@ -723,6 +727,31 @@ class Builder:
             assert residual.C == kout and residual.rows == x.rows and residual.dtype == "bf16"
             ins.append(residual)
         p.add("gemm_mx", ins, out, consts, cite=cite, **attrs)
+        return out
+
+    def lora_delta(self, x: TRef, a_name: str, b_name: str, *, scaling: float, out_scale: Optional[str] = None,
+                   residual: Optional[TRef] = None, cite="", name="") -> TRef:
+        """residual + (x A) (scaling * B [* out_scale]): the low-rank term of a LoRA Dense layer as ONE launch
+        (tfimm_hip_lora_delta; x A stays in registers).  The result goes into the layer's own ``dense`` as its residual, so
+        the adapter's two packed constants ``a`` and ``b`` are the only ones that depend on it (Model.set_lora_weights
+        rewrites them in place).  ``out_scale``: a per-output-channel scale behind the layer (LayerScale), folded into B."""
+        p = self.p
+        a, bm = self.wget(a_name), self.wget(b_name)
+        (kin, r), (r2, kout) = a.shape, bm.shape
+        assert r == r2 and kin == x.C, f"{a_name}: {a.shape} x {bm.shape} on a tensor with C={x.C}"
+        if kin % 8 or kout % 8 or max(kin, kout) > pack.LORA_MAX_DIM or not 1 <= r <= pack.LORA_MAX_RANK:
+            raise NotImplementedError(f"{a_name}: tfimm_hip_lora_delta takes K and N that are multiples of 8 up to {pack.LORA_MAX_DIM} and "
+                                      f"ranks 1..{pack.LORA_MAX_RANK}, got K={kin} N={kout} rank={r}")
+        at, bt = pack.pack_lora(a, bm, scaling, None if out_scale is None else self.wget(out_scale), fp32=self.fp32)
+        consts = {"a": p.new_const(at, a_name + ":lora"), "b": p.new_const(bt, b_name + ":lora")}
+        sp = (x.H, x.W) if x.H * x.W == x.rows else (0, 0)
+        out = p.new_tensor(x.rows, kout, sp[0], sp[1], name=name or b_name + ":delta")
+        ins = [x]
+        if residual is not None:
+            assert residual.C == kout and residual.rows == x.rows and residual.dtype == x.dtype
+            ins.append(residual)
+        p.add("lora_delta", ins, out, consts, cite=cite, rows=x.rows, K=kin, N=kout, Rp=at.shape[0], rank=r,
+              has_residual=residual is not None, a_name=a_name, b_name=b_name, scaling=float(scaling), out_scale=out_scale)
         return out
 
     def empty(self, rows: int, C: int, dtype="bf16", name="") -> TRef:
@@ -1508,6 +1537,17 @@ class Plan:
                 # float32 on both sides under every precision: the same kernel on all three paths (_FP32_SHARED)
                 self.calls.append((lib.tfimm_hip_l2_normalize,
                                    (self.tptr(op.inputs[0]), a["E"], B * a["rows"], a["E"], self.tptr(op.output), a["E"])))
+            elif k == "lora_delta":
+                d = ffi.LoraDesc()
+                x_t, out_t = prog.tensors[op.inputs[0]], prog.tensors[op.output]
+                d.x, d.a, d.b = self.tptr(x_t.id), self.cptr(op.consts["a"]), self.cptr(op.consts["b"])
+                d.out = self.tptr(out_t.id)
+                d.M, d.K, d.N, d.Rp = B * a["rows"], a["K"], a["N"], a["Rp"]
+                d.lda, d.lda_a, d.ldc = x_t.C, a["K"], out_t.C
+                if a["has_residual"]:
+                    d.residual, d.ldr = self.tptr(op.inputs[1]), prog.tensors[op.inputs[1]].C
+                self._keepalive.append(d)
+                self.calls.append((lib.tfimm_hip_lora_delta, (C.byref(d),)))
             else:
                 raise NotImplementedError(k)
 
@@ -1661,6 +1701,9 @@ class Plan:
             # the executor's call table (csrc/plan.hip) has no entry for it: refuse, never emit a blob that skips the op
             raise NotImplementedError("plans that hold the op l2_normalize (tfimm_hip_l2_normalize; EmbeddingModel(..., "
                                       "normalize=True)) are not exported")
+        if any(op.kind == "lora_delta" for op in self.prog.ops):
+            raise NotImplementedError("plans that hold the op lora_delta (tfimm_hip_lora_delta; an unmerged LoRA model) are "
+                                      "not exported: merge the adapter first (merge_lora_weights)")
         if self.device == "cpu":
             raise RuntimeError("export needs a plan built on the GPU (tile hints and occupancy are resolved there)")
         consts = self.prog._dev_consts

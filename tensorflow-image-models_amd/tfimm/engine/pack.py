@@ -62,6 +62,32 @@ def pack_dense(kernel: np.ndarray, bias: Optional[np.ndarray], fp32: bool = Fals
     return wt, b
 
 
+LORA_RANK_PAD = 16   # tfimm_hip_lora_delta: the rank is zero padded to whole 16-wide matrix-unit tiles
+LORA_MAX_RANK = 64
+LORA_MAX_DIM = 8192  # include/tfimm_hip.h TFIMM_LORA_MAX_DIM: the largest K and N of the launch
+
+
+def pack_lora(lora_a: np.ndarray, lora_b: np.ndarray, scaling: float, out_scale: Optional[np.ndarray] = None,
+              fp32: bool = False):
+    """LoRA factors A (in, r) and B (r, out) -> the operands of tfimm_hip_lora_delta: ``a`` [Rp][in] = A transposed and
+    ``b`` [out][Rp] = B' transposed, the rank zero padded to Rp, with B' = scaling * B (* out_scale per output channel: a
+    LayerScale behind the layer) formed in float32; bf16 bits, or float32 for the verification path."""
+    a = np.asarray(lora_a, dtype=np.float32)
+    b = np.asarray(lora_b, dtype=np.float32) * np.float32(scaling)
+    if out_scale is not None:
+        b = b * np.asarray(out_scale, dtype=np.float32).reshape(1, -1)
+    (kin, r), (r2, kout) = a.shape, b.shape
+    assert r == r2 and 1 <= r <= LORA_MAX_RANK, (a.shape, b.shape)
+    rp = ceil_to(r, LORA_RANK_PAD)
+    at = np.zeros((rp, kin), dtype=np.float32)
+    at[:r] = a.T
+    bt = np.zeros((kout, rp), dtype=np.float32)
+    bt[:, :r] = b.T
+    if fp32:
+        return at, bt
+    return to_bf16_bits(at), to_bf16_bits(bt)
+
+
 # ---- MXFP8 (OCP microscaling: e4m3fn elements in blocks of 32 along K, one E8M0 scale per block) ------------------------
 MX_BLOCK = 32
 MX_KPAD = 128        # K-tile of tfimm_hip_gemm_mx: rows of MX operands are zero padded to a multiple of it
