@@ -864,6 +864,81 @@ TFIMM_API int tfimm_hip_score(const float* logits, int64_t ld, int B, int N, con
                               int32_t* pred, float* prob, int64_t* state, int64_t* per_class, uint32_t* confusion, void* stream);
 
 /* =======================================================================================
+ * HEAD FIT (csrc/head_fit.hip): one optimizer step of a classifier head on frozen features, in two launches behind the
+ * logits product -- the linear probe of a pretrained backbone (tfimm.LinearProbe; the CPU restatement of
+ * both rules is tests/head_fit_ref.py).  Both are asynchronous on `stream` and capturable, allocate nothing, use no atomics
+ * and are bit-reproducible from launch to launch; offsets are 64-bit; B == 0 returns 0 and launches nothing.  Float32
+ * logits and master weights under every precision mode: no tfimm_hip_ref_* twin.
+ * ======================================================================================= */
+
+/* tfimm_hip_softmax_grad: per row of logits [B][ld] (float32, N <= ld valid columns) and its label labels[b]:
+ *   grad  bf16 [B][ldg]  grad[b][c] = bf16_rne(p_c - [c == y_b]), p_c = exp(x_c - m) / sum: the softmax of tfimm_hip_score
+ *                        (loader, maximum and sum of csrc/topk_row.h, prob's expression).  A row whose label is -1 or
+ *                        outside [0, N) gets +0.0 in every column.  Only columns [0, N) are written.
+ *   loss  float32 [B], pred int32 [B]: tfimm_hip_score's loss and pred, bit for bit.
+ * One workgroup of 256 threads per row, the row read once and kept in LDS, hence N <= TFIMM_SCORE_MAX_N.
+ * TFIMM_EINVAL before any launch, naming the argument: a NULL pointer; logits / labels / loss / pred not 4-byte aligned; grad
+ * not 16-byte aligned; N outside [1, TFIMM_SCORE_MAX_N]; ld < N; ldg < N or ldg % 8 != 0; B < 0.
+ * Replaces, in a caller of the reference (tfimm/train/problems/classification.py): the backward pass of softmax_loss. */
+TFIMM_API int tfimm_hip_softmax_grad(const float* logits, int64_t ld, int B, int N, const int32_t* labels, void* grad, int64_t ldg,
+                                     float* loss, int32_t* pred, void* stream);
+
+/* tfimm_hip_head_update: the weight gradient of a Dense head and the optimizer step on it in ONE launch; the gradient lives in
+ * the matrix unit's accumulators only.
+ *   f        bf16    [B][ldf]     features, D columns
+ *   g        bf16    [B][ldg]     tfimm_hip_softmax_grad's rows, C columns
+ *   labels   int32   [B]          read only to count n = labels in [0, C)
+ *   w        float32 [C][ldw]     master weights, the head's kernel transposed (the Wt[N][K] layout of tfimm_hip_gemm); in place
+ *   w16      bf16    [C][ldw16]   the shadow tfimm_hip_gemm reads; rewritten
+ *   s1, s2   float32 [C][ldw]     optimizer slots, in place (sgd: momentum, s2 unused and may be NULL; adam: m and v)
+ *   bias, bias_s1, bias_s2  float32 [C]   the same for the bias (no shadow)
+ *   grad_out float32 [C][ldw], bias_grad_out float32 [C]: optional, receive gd
+ *
+ *   acc[c][d] = sum_b g[b][c] * f[b][d]    matrix unit, float32 accumulation, b ascending
+ *   accb[c]   = sum_b g[b][c]              float32, in a fixed order
+ *   inv_n = 1.0f / (float)max(n, 1)
+ *   gd = acc * inv_n
+ *   gr = gd + wd2 * w                      wd2 = 2 * weight_decay
+ *   opt == TFIMM_HEAD_SGD   s1 = mom * s1 - lr * gr ;  w = w + s1                                 (keras SGD, no nesterov)
+ *   opt == TFIMM_HEAD_ADAM  s1 = s1 + (gr - s1) * one_minus_b1 ;  s2 = s2 + (gr * gr - s2) * one_minus_b2 ;
+ *                           w = w - (s1 * lr) / (sqrt(s2) + eps)          (keras Adam; lr is the caller's alpha_t)
+ *   w16 = bf16_rne(w)
+ * Behind acc every operation is one correctly rounded float32 operation in the order written: nothing contracts to a fused
+ * multiply-add, division and square root are the IEEE ones.  mom_or_one_minus_b1 is mom for sgd and 1 - beta1 for adam.
+ * An all-ignored batch (n == 0) is a defined step: gd is zero, weight decay and slot decay act.
+ * Each workgroup owns one 32 x 128 tile of w, walks the whole batch with the accumulators in registers and updates its tile
+ * in place.  Rows >= B and columns >= C / >= D of a ragged tile are masked: no element outside [0, B) x [0, C) of g or
+ * [0, B) x [0, D) of f is read, padding columns of every output are left alone.
+ * TFIMM_EUNSUP: D % 8 != 0 or outside [8, TFIMM_HEAD_MAX_D], C outside [1, TFIMM_HEAD_MAX_C], B > TFIMM_HEAD_MAX_B.
+ * TFIMM_EINVAL: a NULL descriptor or required pointer (adam: s2 and bias_s2), B < 0, an unknown opt, a pitch below its row,
+ * ldf / ldg / ldw16 not a multiple of 8, ldw not a multiple of 4, f / g / w / w16 / s1 / s2 / grad_out not 16-byte aligned,
+ * labels / bias* not 4-byte aligned, any output overlapping another operand.  No launch is made in either case. */
+#define TFIMM_HEAD_SGD 0
+#define TFIMM_HEAD_ADAM 1
+#define TFIMM_HEAD_MAX_D 8192
+#define TFIMM_HEAD_MAX_C 32768
+#define TFIMM_HEAD_MAX_B 65535
+typedef struct tfimm_head_update_desc {
+  const void* f;
+  const void* g;
+  const int32_t* labels;
+  float* w;
+  void* w16;
+  float* s1;
+  float* s2;
+  float* bias;
+  float* bias_s1;
+  float* bias_s2;
+  float* grad_out;
+  float* bias_grad_out;
+  int32_t B, D, C;
+  int32_t ldf, ldg, ldw, ldw16;
+  int32_t opt;
+  float lr, mom_or_one_minus_b1, one_minus_b2, eps, wd2;
+} tfimm_head_update_desc;
+TFIMM_API int tfimm_hip_head_update(const tfimm_head_update_desc* d, void* stream);
+
+/* =======================================================================================
  * EMBEDDING END (csrc/embed.hip): row normalisation of float32 embeddings, and the search of a bf16 gallery
  * ======================================================================================= */
 

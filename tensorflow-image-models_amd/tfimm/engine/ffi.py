@@ -119,6 +119,19 @@ class LoraDesc(C.Structure):
                 ("lda", C.c_int32), ("lda_a", C.c_int32), ("ldr", C.c_int32), ("ldc", C.c_int32)]
 
 
+class HeadUpdateDesc(C.Structure):
+    """tfimm_head_update_desc: the weight gradient of a Dense head and the optimizer step on it (csrc/head_fit.hip)"""
+    _fields_ = [("f", C.c_void_p), ("g", C.c_void_p), ("labels", C.c_void_p),
+                ("w", C.c_void_p), ("w16", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p),
+                ("bias", C.c_void_p), ("bias_s1", C.c_void_p), ("bias_s2", C.c_void_p),
+                ("grad_out", C.c_void_p), ("bias_grad_out", C.c_void_p),
+                ("B", C.c_int32), ("D", C.c_int32), ("C", C.c_int32),
+                ("ldf", C.c_int32), ("ldg", C.c_int32), ("ldw", C.c_int32), ("ldw16", C.c_int32),
+                ("opt", C.c_int32),
+                ("lr", C.c_float), ("mom_or_one_minus_b1", C.c_float), ("one_minus_b2", C.c_float), ("eps", C.c_float),
+                ("wd2", C.c_float)]
+
+
 class ResizeDesc(C.Structure):
     """tfimm_resize_desc: resize + centre crop + normalise of a uint8 batch (csrc/resize.hip)"""
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p),
@@ -229,6 +242,9 @@ SYMBOLS = {
     "tfimm_hip_topk": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     # the scoring end (csrc/score.hip): logits, ld, B, N, labels, loss, rank, pred, prob, state, per_class, confusion
     "tfimm_hip_score": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the head fit (csrc/head_fit.hip): logits, ld, B, N, labels, grad, ldg, loss, pred | descriptor
+    "tfimm_hip_softmax_grad": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "tfimm_hip_head_update": (_i, [C.POINTER(HeadUpdateDesc), _vp]),
     # the embedding end (csrc/embed.hip): x, ld_x, B, E, y, ld_y | B, N, E, k, chunk |
     # q, ld_q, B, g, ld_g, N, E, k, chunk, scores, indices, workspace, workspace_bytes
     "tfimm_hip_l2_normalize": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
@@ -358,6 +374,10 @@ TOPK_MAX_K, TOPK_MAX_N = 64, 32768
 SCORE_MAX_N, SCORE_MAX_CONFUSION_N, SCORE_IGNORE = TOPK_MAX_N, 4096, -1
 SCORE_SCORED, SCORE_IGNORED, SCORE_INVALID, SCORE_LOSS_EXCLUDED, SCORE_LOSS_Q, SCORE_RANK_HIST = 0, 1, 2, 3, 4, 5
 SCORE_RANK_BINS, SCORE_STATE_WORDS = 65, 70
+
+# include/tfimm_hip.h: the optimizers and the domain of tfimm_hip_head_update
+HEAD_SGD, HEAD_ADAM = 0, 1
+HEAD_MAX_D, HEAD_MAX_C, HEAD_MAX_B = 8192, 32768, 65535
 
 # include/tfimm_hip.h: the domain of tfimm_hip_embed_search (E a multiple of 16; the gallery row pitch a multiple of 8 elements)
 EMBED_MIN_E, EMBED_MAX_E, EMBED_MAX_K = 16, 2048, 64

@@ -540,6 +540,45 @@ class Model:
         labels = self._check_evaluate(x, labels, meter)
         return _score(self(x), labels, meter, f"{self.name}: evaluate")
 
+    def _head_input(self, x, training: bool = False) -> Tensor:
+        """What the classifier of ``model(x)`` reads, (B, D): ``forward_features(x)``, a feature map (B, H, W, D) averaged
+        over H and W (tfimm_hip_mean_rows, as the model's own head does).  Takes everything ``__call__`` takes."""
+        import ctypes as C
+        import torch
+        from ..engine import ffi
+        f = self.forward_features(x, training=training).torch()
+        if f.ndim == 2:
+            return Tensor(f)
+        if f.ndim != 4:
+            raise ValueError(f"{self.name}: forward_features is {tuple(f.shape)}: several feature rows per image, no single "
+                             f"classifier input")
+        B, H, W, D = f.shape
+        f = f.contiguous()
+        pooled = torch.empty((B, D), dtype=f.dtype, device=f.device)
+        if B:
+            bf16 = f.dtype == torch.bfloat16
+            mean = ffi.lib.tfimm_hip_mean_rows if bf16 else ffi.lib.tfimm_hip_ref_mean_rows
+            ffi.check(mean(f.data_ptr(), pooled.data_ptr(), B, H * W, D, 0 if bf16 else 1,
+                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "tfimm_hip_mean_rows")
+        return Tensor(pooled)
+
+    def fit_head(self, x, labels, probe, training: bool = False):
+        """One step of a ``tfimm.LinearProbe`` on this model's frozen features: ``probe.step(_head_input(x), labels)``.  Takes
+        everything ``__call__`` takes; the model's weights, programs, plans and recordings are not touched
+        (``probe.install(model)`` hands the fitted head over).  Returns ``StepResult(loss, pred)``, each (B,), without waiting
+        for the device.  ``ValueError`` before any device work for a model whose logits hold several heads."""
+        if training:
+            raise NotImplementedError("This engine implements the inference forward path only (training=False).")
+        from .meter import _labels
+        n = int(self.cfg.nb_classes)
+        if n > 0:
+            heads = self.program().outputs["logits"].C // n          # (lowering is host work)
+            if heads != 1:
+                raise ValueError(f"{self.name}: the logits hold {heads} heads per image; fit_head fits one")
+        batch = len(x.data) if isinstance(x, DeferredInput) and x.mixed else len(x) if isinstance(x, (list, tuple)) else x.shape[0]
+        labels = _labels(labels, int(batch), f"{self.name}: fit_head")
+        return probe.step(self._head_input(x), labels)
+
     def forward_features(self, x, training: bool = False, return_features: bool = False):
         if training:
             raise NotImplementedError("This engine implements the inference forward path only (training=False).")
