@@ -425,6 +425,83 @@ TFIMM_API int tfimm_hip_preprocess_resize_batch(const tfimm_resize_batch_desc* d
 TFIMM_API int tfimm_hip_preprocess_resize_batch_aa(const tfimm_resize_batch_aa_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * tfimm_hip_preprocess_regions / _regions_aa: the two launches above for BOXES inside larger frames (csrc/resize_regions.hip;
+ * DESIGN.md 3.22) -- what create_preprocessing(..., resize=True) runs for pre(frames, boxes=...).  Box n with integer pixel
+ * corners (y0, x0, y1, x1) covers rows [y0, y1) and columns [x0, x1) of frame box_frame[n] and is an image of its own: the
+ * result is, bit for bit, what tfimm_hip_preprocess_resize_batch[_aa] computes for the slice packed on its own -- the same
+ * geometry (of the box's size), the same tables, the same float32 operations, the same normalisation and rounding, the same
+ * two output layouts.  Taps beyond the box edge clamp to the BOX: no pixel outside it contributes.
+ *
+ * What differs is the addressing.  Every frame lies ONCE in the arena, however many boxes name it, and a record says where
+ * its box starts and how far apart two rows are:
+ *   in     one uint8 arena of in_bytes bytes; frame f is packed [Hf][Wf][c_in] at any byte offset
+ *   recs   B records tfimm_resize_region_rec, one per box: the fields of tfimm_resize_batch_rec with
+ *            in_offset  the byte offset of the box's FIRST PIXEL: the frame's offset + (y0 * Wf + x0) * c_in
+ *            row_pitch  the bytes between two rows: Wf * c_in of the box's frame
+ *            Hs, Ws     the size of the BOX
+ *   tables exactly those of tfimm_hip_preprocess_resize_batch[_aa] for images of the boxes' sizes
+ * The kernels trust none of it, as above; the row pitch is clamped to [1, 2^24 * TFIMM_PREPROCESS_MAX_CHANNELS].  Launch
+ * shapes, LDS size and refusals are those of tfimm_hip_preprocess_resize_batch[_aa].
+ * ------------------------------------------------------------------------------------- */
+typedef struct tfimm_resize_region_rec {
+  int64_t in_offset;       /* byte offset of the box's first pixel in the pixel arena */
+  int64_t row_pitch;       /* bytes between two rows of the box: a row of its frame */
+  int32_t Hs, Ws;          /* the size of the box */
+  int32_t y_tab, x_tab;    /* as in tfimm_resize_batch_rec, from here on */
+  int32_t y_w, x_w;
+  int32_t y_taps, x_taps;
+  int32_t tile_rows;
+  int32_t cols_max;
+  int32_t tile0, n_tiles;
+} tfimm_resize_region_rec;
+
+typedef struct tfimm_resize_region_desc {
+  const void* in;          /* uint8 arena, in_bytes bytes: the frames */
+  const tfimm_resize_region_rec* recs;   /* DEVICE [B] */
+  void* out;               /* bf16 (tfimm_hip_ref_preprocess_regions: float32), the layouts of tfimm_resize_desc.out */
+  const int32_t* idx;      /* DEVICE [B * (H + W) * taps] */
+  const float* w;          /* DEVICE [B * (H + W) * taps] */
+  const float* mean_host;  /* HOST arrays of c_in floats (copied into the launch) */
+  const float* std_host;
+  int64_t in_bytes;
+  int32_t B, c_in, H, W, c_out;   /* B: the number of boxes */
+  int32_t pad_t, pad_b, pad_l, pad_r;
+  int32_t taps;            /* 2 = bilinear, 4 = bicubic */
+} tfimm_resize_region_desc;
+
+typedef struct tfimm_resize_region_aa_desc {
+  const void* in;          /* uint8 arena, in_bytes bytes: the frames */
+  const tfimm_resize_region_rec* recs;   /* DEVICE [B] */
+  void* out;
+  const int32_t* start;    /* DEVICE [B * (H + W)] */
+  const int32_t* count;    /* DEVICE [B * (H + W)] */
+  const float* w;          /* DEVICE [w_floats] */
+  const float* mean_host;
+  const float* std_host;
+  int64_t in_bytes;
+  int64_t w_floats;        /* capacity of the weight arena */
+  int32_t B, c_in, H, W, c_out;
+  int32_t pad_t, pad_b, pad_l, pad_r;
+  int32_t taps_cap;        /* the largest pitch a record may name, <= TFIMM_RESIZE_AA_MAX_TAPS */
+  int32_t lds_bytes;       /* dynamic LDS of a workgroup, a multiple of 4 and <= 64 KiB; 0 = 64 KiB */
+} tfimm_resize_region_aa_desc;
+
+/* Records and tables of N boxes in F frames, built over tfimm_hip_resize_batch_tables (and so over tfimm_hip_resize_taps and
+ * tfimm_hip_resize_spans).  A plain host function: no GPU is needed or touched.  frame_hw: [F][2] = (Hf, Wf); boxes: [N][4] =
+ * (y0, x0, y1, x1); box_frame: [N] frame indices, in any order, repeats allowed; geometry: [N][4] = (Rh, Rw, top, left) of
+ * every box's own size; the other arguments and the arrays written as in tfimm_hip_resize_batch_tables with B = N.  The
+ * frames are packed ONCE each, back to back in list order: sizes->in_bytes is the sum of Hf * Wf * c_in over the F frames.
+ * Refused with the invalid-argument code and nothing written: an empty box, a box outside its frame, a frame index out of
+ * range (the message names the box).  A box outside the antialias domain is named in sizes->bad_image (sizes is filled,
+ * nothing else written) and the call returns the invalid-argument code. */
+TFIMM_API int tfimm_hip_resize_region_tables(int F, const int32_t* frame_hw, int N, const int32_t* boxes,
+                                             const int32_t* box_frame, const int32_t* geometry, int H, int W, int c_in,
+                                             const int32_t* pad, int method, int antialias, tfimm_resize_batch_sizes* sizes,
+                                             tfimm_resize_region_rec* recs, int32_t* tab_a, int32_t* tab_b, float* w);
+TFIMM_API int tfimm_hip_preprocess_regions(const tfimm_resize_region_desc* d, void* stream);
+TFIMM_API int tfimm_hip_preprocess_regions_aa(const tfimm_resize_region_aa_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * tfimm_hip_layernorm: y[r][:] = (x[r][:] - mean) * rsqrt(var + eps) * gamma + beta,
  * population variance, fp32 statistics.  x row r starts at x + r*x_stride (elements),
  * y row r at y + r*y_stride.  Replaces tf.keras.layers.LayerNormalization
@@ -1036,6 +1113,9 @@ TFIMM_API int tfimm_hip_ref_preprocess_resize_aa(const tfimm_resize_aa_desc* d, 
 /* tfimm_hip_preprocess_resize_batch / _batch_aa with a float32 `out` (same descriptors, same device code) */
 TFIMM_API int tfimm_hip_ref_preprocess_resize_batch(const tfimm_resize_batch_desc* d, void* stream);
 TFIMM_API int tfimm_hip_ref_preprocess_resize_batch_aa(const tfimm_resize_batch_aa_desc* d, void* stream);
+/* tfimm_hip_preprocess_regions / _regions_aa with a float32 `out` (same descriptors, same device code) */
+TFIMM_API int tfimm_hip_ref_preprocess_regions(const tfimm_resize_region_desc* d, void* stream);
+TFIMM_API int tfimm_hip_ref_preprocess_regions_aa(const tfimm_resize_region_aa_desc* d, void* stream);
 TFIMM_API int tfimm_hip_ref_layernorm(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int d,
                                       int64_t x_stride, int64_t y_stride, float eps, void* stream);
 TFIMM_API int tfimm_hip_ref_patch_merge_ln(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W,

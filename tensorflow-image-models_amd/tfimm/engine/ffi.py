@@ -185,6 +185,21 @@ class ResizeBatchAADesc(C.Structure):
                 ("taps_cap", C.c_int32), ("lds_bytes", C.c_int32)]
 
 
+class ResizeRegionRec(C.Structure):
+    """tfimm_resize_region_rec: where one box inside a larger frame and its tables live (csrc/resize_regions.hip)"""
+    _fields_ = [("in_offset", C.c_int64), ("row_pitch", C.c_int64)] + ResizeBatchRec._fields_[1:]
+
+
+class ResizeRegionDesc(C.Structure):
+    """tfimm_resize_region_desc: resize + centre crop + normalise of boxes inside uint8 frames (csrc/resize_regions.hip)"""
+    _fields_ = ResizeBatchDesc._fields_
+
+
+class ResizeRegionAADesc(C.Structure):
+    """tfimm_resize_region_aa_desc: the antialiased launch over boxes inside uint8 frames (csrc/resize_regions.hip)"""
+    _fields_ = ResizeBatchAADesc._fields_
+
+
 class ResizeBatchSizes(C.Structure):
     """tfimm_resize_batch_sizes: what tfimm_hip_resize_batch_tables reports"""
     _fields_ = [("in_bytes", C.c_int64), ("tab_elems", C.c_int64), ("w_floats", C.c_int64), ("n_tiles", C.c_int64),
@@ -218,6 +233,11 @@ SYMBOLS = {
                                            C.POINTER(ResizeBatchSizes), _vp, _vp, _vp, _vp]),
     "tfimm_hip_preprocess_resize_batch": (_i, [C.POINTER(ResizeBatchDesc), _vp]),
     "tfimm_hip_preprocess_resize_batch_aa": (_i, [C.POINTER(ResizeBatchAADesc), _vp]),
+    "tfimm_hip_resize_region_tables": (_i, [_i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), _i, _i,
+                                            C.POINTER(ResizeBatchSizes), _vp, _vp, _vp, _vp]),
+    "tfimm_hip_preprocess_regions": (_i, [C.POINTER(ResizeRegionDesc), _vp]),
+    "tfimm_hip_preprocess_regions_aa": (_i, [C.POINTER(ResizeRegionAADesc), _vp]),
     "tfimm_hip_row_stats": (_i, [_vp, _vp, _i64, _i, _i64, _f, _vp]),
     "tfimm_hip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
     "tfimm_hip_attention": (_i, [C.POINTER(AttnDesc), _vp]),
@@ -265,6 +285,8 @@ SYMBOLS = {
     "tfimm_hip_ref_preprocess_resize_aa": (_i, [C.POINTER(ResizeAADesc), _vp]),
     "tfimm_hip_ref_preprocess_resize_batch": (_i, [C.POINTER(ResizeBatchDesc), _vp]),
     "tfimm_hip_ref_preprocess_resize_batch_aa": (_i, [C.POINTER(ResizeBatchAADesc), _vp]),
+    "tfimm_hip_ref_preprocess_regions": (_i, [C.POINTER(ResizeRegionDesc), _vp]),
+    "tfimm_hip_ref_preprocess_regions_aa": (_i, [C.POINTER(ResizeRegionAADesc), _vp]),
     "tfimm_hip_ref_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
     "tfimm_hip_ref_patch_merge_ln": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "tfimm_hip_ref_copy_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -461,6 +483,92 @@ def resize_batch_tables(sizes, geometries, size, method: str, antialias: bool = 
     check(lib.tfimm_hip_resize_batch_tables(*args, C.byref(need), recs.ctypes.data, tab_a.ctypes.data,
                                             tab_b.ctypes.data if antialias else None, w.ctypes.data),
           "tfimm_hip_resize_batch_tables")
+    out = {"recs": recs, "w": w, "in_bytes": int(need.in_bytes), "max_taps": int(need.max_taps),
+           "lds_floats": int(need.lds_floats), "n_tiles": int(need.n_tiles)}
+    if antialias:
+        out["start"], out["count"] = tab_a, tab_b
+    else:
+        out["idx"] = tab_a
+    return out
+
+
+#: numpy view of tfimm_resize_region_rec
+RESIZE_REGION_REC = [("in_offset", "<i8"), ("row_pitch", "<i8")] + RESIZE_BATCH_REC[1:]
+
+
+def check_boxes(frames_hw, boxes, box_indices=None):
+    """The boxes of ``pre(frames, boxes=..., box_indices=...)`` as ``(boxes int32 (N, 4), box_indices int32 (N,))`` --
+    ``boxes[n] = (y0, x0, y1, x1)`` covers rows ``[y0, y1)`` and columns ``[x0, x1)`` of frame ``box_indices[n]``.
+    ``ValueError`` naming the box for float coordinates (the caller rounds on purpose), a wrong shape, no box at all, an
+    empty box, a box outside its frame and a frame index out of range; ``box_indices`` defaults to zeros for ONE frame."""
+    import numpy as np
+    hw = np.asarray(frames_hw, np.int64).reshape(-1, 2)
+    b = np.asarray(boxes)
+    if b.dtype.kind not in "iu":
+        raise ValueError(f"boxes must be integer pixel corners (y0, x0, y1, x1), got dtype {b.dtype}: round them on purpose")
+    if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] == 0:
+        raise ValueError(f"boxes must have shape (N, 4) with N >= 1, got {b.shape}")
+    if box_indices is None:
+        if hw.shape[0] != 1:
+            raise ValueError(f"box_indices is required with {hw.shape[0]} frames: it says which frame every box lies in")
+        idx = np.zeros(b.shape[0], np.int64)
+    else:
+        idx = np.asarray(box_indices)
+        if idx.dtype.kind not in "iu" or idx.shape != (b.shape[0],):
+            raise ValueError(f"box_indices must be {b.shape[0]} integers, got shape {idx.shape}, dtype {idx.dtype}")
+    b, idx = b.astype(np.int64), idx.astype(np.int64)
+    no_frame = (idx < 0) | (idx >= hw.shape[0])
+    Hf, Wf = hw[np.where(no_frame, 0, idx)].T
+    empty = (b[:, 2] <= b[:, 0]) | (b[:, 3] <= b[:, 1])
+    outside = (b[:, 0] < 0) | (b[:, 1] < 0) | (b[:, 2] > Hf) | (b[:, 3] > Wf)
+    bad = no_frame | empty | outside
+    if bad.any():                                        # the first bad box, by what is wrong with it
+        n = int(np.argmax(bad))
+        y0, x0, y1, x1 = (int(v) for v in b[n])
+        if no_frame[n]:
+            raise ValueError(f"box {n} names frame {int(idx[n])} of {hw.shape[0]}")
+        if empty[n]:
+            raise ValueError(f"box {n} ({y0}, {x0}, {y1}, {x1}) is empty")
+        raise ValueError(f"box {n} ({y0}, {x0}, {y1}, {x1}) lies outside its frame {int(idx[n])} ({int(Hf[n])} x {int(Wf[n])})")
+    return np.ascontiguousarray(b, np.int32), np.ascontiguousarray(idx, np.int32)
+
+
+def resize_region_tables(frames_hw, boxes, box_indices, geometries, size, method: str, antialias: bool = False, *,
+                         c_in: int = 3, pad=(0, 0, 0, 0)):
+    """tfimm_hip_resize_region_tables as numpy arrays -- records and table arenas of boxes inside larger frames
+    (``frames_hw[f] = (Hf, Wf)``, ``boxes[n] = (y0, x0, y1, x1)`` in frame ``box_indices[n]``, ``geometries[n] = (Rh, Rw, top,
+    left)`` of the box's own size), all going to the crop window ``size``; a host function, no GPU involved.  Returns the dict
+    of ``resize_batch_tables`` with ``recs`` structured as ``RESIZE_REGION_REC``; ``in_bytes`` is the sum of the FRAMES'
+    bytes, each frame packed once.  ``ValueError`` naming the box for a box that is empty, outside its frame, names no frame
+    or lies outside the antialias domain."""
+    import numpy as np
+    hw = np.ascontiguousarray(np.asarray(frames_hw, np.int32).reshape(-1, 2))
+    bx, idx = check_boxes(hw, boxes, box_indices)
+    geo = np.ascontiguousarray(np.asarray(geometries, np.int32).reshape(-1, 4))
+    N = bx.shape[0]
+    if geo.shape[0] != N:
+        raise ValueError(f"resize_region_tables: {N} boxes and {geo.shape[0]} geometries")
+    pads = (C.c_int32 * 4)(*[int(v) for v in pad])
+    i32p = C.POINTER(C.c_int32)
+    args = (hw.shape[0], hw.ctypes.data_as(i32p), N, bx.ctypes.data_as(i32p), idx.ctypes.data_as(i32p), geo.ctypes.data_as(i32p),
+            int(size[0]), int(size[1]), int(c_in), pads, RESIZE_METHODS[method], 1 if antialias else 0)
+    need = ResizeBatchSizes()
+    need.bad_image = -1
+    rc = lib.tfimm_hip_resize_region_tables(*args, C.byref(need), None, None, None, None)
+    if rc != 0 and need.bad_image >= 0:
+        i = need.bad_image
+        raise ValueError(f"antialiased {method} resize: box {i} ({bx[i, 2] - bx[i, 0]} x {bx[i, 3] - bx[i, 1]} -> {geo[i, 0]} x "
+                         f"{geo[i, 1]}) needs more than TFIMM_RESIZE_AA_MAX_TAPS = {RESIZE_AA_MAX_TAPS} taps per output pixel: "
+                         "the box is too large for the device resize, shrink the frame on the host first")
+    check(rc, "tfimm_hip_resize_region_tables")
+    recs = np.zeros(N, np.dtype(RESIZE_REGION_REC))
+    assert recs.itemsize == C.sizeof(ResizeRegionRec)
+    tab_a = np.zeros(need.tab_elems, np.int32)
+    tab_b = np.zeros(need.tab_elems if antialias else 0, np.int32)
+    w = np.zeros(need.w_floats, np.float32)
+    check(lib.tfimm_hip_resize_region_tables(*args, C.byref(need), recs.ctypes.data, tab_a.ctypes.data,
+                                             tab_b.ctypes.data if antialias else None, w.ctypes.data),
+          "tfimm_hip_resize_region_tables")
     out = {"recs": recs, "w": w, "in_bytes": int(need.in_bytes), "max_taps": int(need.max_taps),
            "lds_floats": int(need.lds_floats), "n_tiles": int(need.n_tiles)}
     if antialias:

@@ -1192,6 +1192,18 @@ class _Mixed:
 MIXED = _Mixed()
 
 
+class _Regions:
+    """The input of ``Plan.run`` / ``Plan.capture`` for boxes inside larger frames: the frames, the records and the tables
+    are what ``Plan.stage_regions`` last put into the plan's own buffers."""
+    dtype = "torch.uint8"
+
+    def __repr__(self):
+        return "REGIONS"
+
+
+REGIONS = _Regions()
+
+
 def _grown(need: int, have: int, floor: int) -> int:
     """capacity after growth by doubling: the smallest ``floor * 2 ** k`` that holds ``need`` (``have`` when it does)"""
     cap = max(have, floor)
@@ -1235,6 +1247,8 @@ class Plan:
         #: norm -> the state of the mixed-size input step (``stage_mixed``): descriptor, device buffers for the pixel arena,
         #: the records and the tables, their capacities
         self._mixed: Dict[tuple, dict] = {}
+        #: norm -> the same state of the region input step (``stage_regions``)
+        self._regions: Dict[tuple, dict] = {}
         self._gemm_descs = []
         self._gemm_call_index = []
         self._tune_times = {}          # shape key -> {hint: ms} of the last isolated autotune
@@ -1694,7 +1708,7 @@ class Plan:
         import torch
         if self.prog.precision == "fp32":
             raise NotImplementedError("plans of the float32 verification path are not exported")
-        if self._resize_tabs or self._mixed:
+        if self._resize_tabs or self._mixed or self._regions:
             raise NotImplementedError("plans run with a resize spec are not exported: tfimm_hip_plan_forward takes float32 / "
                                       "bf16 images of the program's input size only")
         if any(op.kind == "l2_normalize" for op in self.prog.ops):
@@ -1877,6 +1891,11 @@ class Plan:
                 d, padded_ptr = self._stem_raw[:2]          # the fused stem reads the converted copy, as for every uint8 input
                 d.x, d.in_dtype = padded_ptr, 0
             return self._launch_mixed(st, norm)
+        if x_dev is REGIONS:
+            if self.prog.precision != "fp32" and self._stem_raw is not None:
+                d, padded_ptr = self._stem_raw[:2]
+                d.x, d.in_dtype = padded_ptr, 0
+            return self._launch_regions(st, norm)
         if (x_dev.dtype == torch.uint8) != (norm is not None):
             raise TypeError("uint8 input needs norm=(mean, std); float input must not pass it")
         resize = None
@@ -1971,10 +1990,9 @@ class Plan:
         weight arena, span pitch, LDS) grow by doubling; returns True when one grew, i.e. when a recording of this step no
         longer points at the live buffers.  ``ValueError`` before anything is uploaded when an image lies outside the
         antialias domain."""
-        import torch
         from ..models.factory import resize_geometry
         ffi = self.ffi
-        mean, std, (method, crop_pct, *aa) = norm
+        _, _, (method, crop_pct, *aa) = norm
         aa = bool(aa and aa[0])
         H, W, _ = self.prog.input_shape
         c_in = self._input_patch[3]
@@ -1985,10 +2003,55 @@ class Plan:
         sizes = [im.shape[:2] for im in images]
         tabs = ffi.resize_batch_tables(sizes, [resize_geometry(s, (H, W), crop_pct) for s in sizes], (H, W), method, aa,
                                        c_in=c_in, pad=pad)
-        st = self._mixed.get(norm)
+        return self._stage_records(self._mixed, norm, tabs, images, pad, ffi.ResizeBatchRec,
+                                   ffi.ResizeBatchAADesc if aa else ffi.ResizeBatchDesc)
+
+    def stage_regions(self, frames, boxes, box_indices, norm) -> bool:
+        """The host half of the region input step (tfimm_hip_preprocess_regions[_aa]): ``frames`` is a list of
+        contiguous uint8 arrays (Hf, Wf, C), ``boxes`` an integer array (``self.batch``, 4) of corners (y0, x0, y1, x1) and
+        ``box_indices`` the frame of every box; ``norm`` as for ``stage_mixed``.  Every box is an image of its own: geometry and
+        tables are those of the slice.  Only the frames this chunk of boxes names are packed and uploaded, each ONCE, however
+        many boxes lie in it; records and tables follow as in ``stage_mixed``, into buffers of the same doubling capacities.
+        The launch -- ``run(REGIONS, norm=norm)`` or a recording of it -- reads those buffers and nothing else.  Returns True
+        when a buffer grew.  ``ValueError`` before anything is uploaded for a bad box and for a box outside the antialias
+        domain."""
+        from ..models.factory import resize_geometry
+        ffi = self.ffi
+        _, _, (method, crop_pct, *aa) = norm
+        aa = bool(aa and aa[0])
+        H, W, _ = self.prog.input_shape
+        c_in = self._input_patch[3]
+        if any(f.ndim != 3 or f.shape[2] != c_in or f.dtype != np.uint8 for f in frames):
+            raise ValueError(f"region resize input: frames must be uint8 (Hf, Wf, {c_in})")
+        boxes, box_indices = ffi.check_boxes([f.shape[:2] for f in frames], boxes, box_indices)
+        if boxes.shape[0] != self.batch:
+            raise ValueError(f"region resize input of {boxes.shape[0]} boxes for a plan of batch {self.batch}")
+        # the frames this chunk names, in list order, and the boxes' indices into them
+        used, local = np.unique(box_indices, return_inverse=True)
+        used_frames = [frames[int(f)] for f in used]
+        fp32 = self.prog.precision == "fp32"
+        pad = (0, 0, 0, 0) if fp32 else tuple(self._input_pad)
+        geo = [resize_geometry((int(b[2] - b[0]), int(b[3] - b[1])), (H, W), crop_pct) for b in boxes]
+        tabs = ffi.resize_region_tables([f.shape[:2] for f in used_frames], boxes, local.astype(np.int32), geo, (H, W), method,
+                                        aa, c_in=c_in, pad=pad)
+        return self._stage_records(self._regions, norm, tabs, used_frames, pad, ffi.ResizeRegionRec,
+                                   ffi.ResizeRegionAADesc if aa else ffi.ResizeRegionDesc)
+
+    def _stage_records(self, store, norm, tabs, sources, pad, rec_cls, desc_cls) -> bool:
+        """What ``stage_mixed`` and ``stage_regions`` share: the descriptor and the device buffers of ``store[norm]``, grown by
+        doubling where ``tabs`` (ffi.resize_batch_tables / resize_region_tables) needs more; ``sources`` -- the arrays the
+        records' offsets count over -- packed back to back into the pinned staging buffer and uploaded, then records and
+        tables.  Returns True when a buffer grew."""
+        import torch
+        ffi = self.ffi
+        mean, std, (method, _, *aa) = norm
+        aa = bool(aa and aa[0])
+        H, W, _ = self.prog.input_shape
+        c_in = self._input_patch[3]
+        st = store.get(norm)
         grew = False
         if st is None:
-            d = ffi.ResizeBatchAADesc() if aa else ffi.ResizeBatchDesc()
+            d = desc_cls()
             host = ((C.c_float * c_in)(*[float(v) for v in mean]), (C.c_float * c_in)(*[float(v) for v in std]))
             d.mean_host, d.std_host = host
             d.out = self._input_patch[1]
@@ -1996,7 +2059,7 @@ class Plan:
             d.pad_t, d.pad_b, d.pad_l, d.pad_r = pad
             if not aa:
                 d.taps = 4 if method == "bicubic" else 2
-            st = self._mixed[norm] = {"desc": d, "host": host, "aa": aa, "arena_cap": 0, "w_cap": 0, "taps_cap": 0, "lds_cap": 0}
+            st = store[norm] = {"desc": d, "host": host, "aa": aa, "arena_cap": 0, "w_cap": 0, "taps_cap": 0, "lds_cap": 0}
             grew = True
         d = st["desc"]
         # -- capacities: doubling, so that a stream of batches settles after a few growths
@@ -2007,7 +2070,7 @@ class Plan:
             st["stage"] = torch.empty(arena_cap, dtype=torch.uint8, pin_memory=self.device != "cpu")
             st["arena_cap"], grew = arena_cap, True
             d.in_, d.in_bytes = st["arena"].data_ptr(), arena_cap
-        n_rec = self.batch * C.sizeof(ffi.ResizeBatchRec)
+        n_rec = self.batch * C.sizeof(rec_cls)
         n_tab = tabs["idx"].size if not aa else tabs["start"].size
         if w_cap != st["w_cap"]:
             # one buffer: records | idx (or start | count) | weights -- everything but the weights has a fixed size
@@ -2029,7 +2092,7 @@ class Plan:
                 d.taps_cap, d.lds_bytes = taps_cap, lds_cap
         # -- pack and upload: the pixels back to back in list order (the offsets of the records), then records and tables
         stage, pos = st["stage"].numpy(), 0
-        for im in images:
+        for im in sources:
             stage[pos:pos + im.size] = im.reshape(-1)
             pos += im.size
         assert pos == tabs["in_bytes"]
@@ -2050,6 +2113,14 @@ class Plan:
         if m is None:
             raise RuntimeError("run(MIXED) before stage_mixed: the plan holds no mixed batch for this norm")
         fn = "tfimm_hip_ref_preprocess_resize_batch" if self.prog.precision == "fp32" else "tfimm_hip_preprocess_resize_batch"
+        return getattr(self.ffi.lib, fn + ("_aa" if m["aa"] else ""))(C.byref(m["desc"]), st)
+
+    def _launch_regions(self, st, norm) -> int:
+        """the device half of ``stage_regions``: one launch over whatever it last uploaded"""
+        m = self._regions.get(norm)
+        if m is None:
+            raise RuntimeError("run(REGIONS) before stage_regions: the plan holds no boxes for this norm")
+        fn = "tfimm_hip_ref_preprocess_regions" if self.prog.precision == "fp32" else "tfimm_hip_preprocess_regions"
         return getattr(self.ffi.lib, fn + ("_aa" if m["aa"] else ""))(C.byref(m["desc"]), st)
 
     def run(self, x_dev, stream_ptr: Optional[int] = None, norm=None, lo: int = 0, hi: Optional[int] = None):

@@ -100,7 +100,7 @@ def resize_geometry(src_hw, input_size, crop_pct: float):
 
 def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
                          dtype: Optional[str] = None, defer: bool = False, resize: bool = False,
-                         antialias: bool = False) -> Callable:
+                         antialias: bool = False, crop_pct: Optional[float] = None) -> Callable:
     """Function mapping [0, 255] images to model inputs: ``(img / 255 - mean) / std`` with
     mean/std tiled to ``in_channels`` (factory.py:153-169).  Works on numpy arrays and torch
     tensors, single images and batches; returns the input's array type.
@@ -134,7 +134,22 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
     (tfimm_hip_preprocess_resize_batch[_aa]): per model, batch size and precision there is one plan and one
     recording for every mix of sizes, so streaming a folder of photos does not grow device memory with the number of
     sizes.  Same arithmetic as for an array, image by image, bit for bit.  A list without ``resize=True``, an empty list, a
-    member that is not uint8, not 3-D or of another channel count raises ``ValueError``."""
+    member that is not uint8, not 3-D or of another channel count raises ``ValueError``.
+
+    BOXES of frames, ``pre(frames, boxes=b, box_indices=i)`` with ``resize=True``: ``frames`` is one uint8 ``(Hf, Wf, C)`` frame,
+    an ``(F, Hf, Wf, C)`` array or a list of frames of different sizes; ``boxes`` is an integer array-like ``(N, 4)`` of pixel
+    corners ``(y0, x0, y1, x1)`` -- box ``n`` covers rows ``[y0, y1)`` and columns ``[x0, x1)`` of frame ``box_indices[n]``;
+    ``box_indices`` ``(N,)`` may be in any order and repeat, and defaults to zeros for one frame.  The batch is the boxes
+    (``shape`` is ``(N, None, None, C)``) and every box is an image of its own: ``model(pre(frames, boxes=b))`` computes, bit
+    for bit, what ``model(pre([frames[i][y0:y1, x0:x1], ...]))`` computes -- taps beyond a box's edge clamp to the box -- but
+    uploads every frame once, however many boxes lie in it, and slices nothing on the host (tfimm_hip_preprocess_regions[_aa],
+    DESIGN.md 3.22); one plan and one recording per model, ``N`` and precision.  ``ValueError`` before anything is uploaded for
+    boxes without ``resize=True``, float boxes (round them on purpose), ``N == 0``, a box that is empty or outside its frame,
+    a frame index out of range, frames that are not uint8 or of another channel count.
+
+    ``crop_pct`` (needs ``resize=True``; in (0, 1]): replaces the config's ``crop_pct`` in the resize spec of every form.  A
+    detector's boxes usually want ``1.0``: the config's value (0.875 for most models) cuts their rim.  ``None`` keeps the
+    config's value."""
     if not is_model(model_name):
         raise ValueError(f"Unknown model: {model_name}.")
     cfg = model_config(model_name)
@@ -143,6 +158,11 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
                          "model's input conversion; there is no host resize path")
     if antialias and not resize:
         raise ValueError("create_preprocessing(antialias=True) needs resize=True: antialiasing is part of the device resize")
+    if crop_pct is not None:
+        if not resize:
+            raise ValueError("create_preprocessing(crop_pct=...) needs resize=True: the crop is part of the device resize")
+        if isinstance(crop_pct, bool) or not 0.0 < float(crop_pct) <= 1.0:
+            raise ValueError(f"create_preprocessing: crop_pct = {crop_pct!r} must be in (0, 1]")
     if resize and cfg.interpolation not in ("bicubic", "bilinear"):
         raise ValueError(f"{model_name}: interpolation '{cfg.interpolation}' is not supported (bicubic, bilinear)")
     out_dtype = np.dtype(dtype or "float32")
@@ -154,6 +174,38 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
         return np.tile(v, reps)[:n]
 
     mean, std = _adapt(cfg.mean), _adapt(cfg.std)
+
+    def _spec():
+        """the resize spec of a DeferredInput: (interpolation, crop_pct, input_size[, True])"""
+        pct = float(cfg.crop_pct if crop_pct is None else crop_pct)
+        return (cfg.interpolation, pct, tuple(int(v) for v in cfg.input_size)) + ((True,) if antialias else ())
+
+    def _regions(frames, boxes, box_indices):
+        """boxes inside one frame, a stack of frames or a list of frames: one DeferredInput whose batch is the boxes"""
+        from ..engine.ffi import check_boxes
+        from .model import DeferredInput
+        if not resize:
+            raise ValueError("boxes need create_preprocessing(defer=True, resize=True): a box is cropped by the device resize")
+        if isinstance(frames, (list, tuple)):
+            frames = list(frames)
+        elif len(getattr(frames, "shape", ())) == 3:
+            frames = [frames]
+        elif len(getattr(frames, "shape", ())) == 4:
+            frames = [frames[i] for i in range(frames.shape[0])]
+        else:
+            raise ValueError(f"frames must be a uint8 (Hf, Wf, {n}) frame, an (F, Hf, Wf, {n}) array or a list of frames, got "
+                             f"{getattr(frames, 'shape', type(frames).__name__)}")
+        if len(frames) == 0:
+            raise ValueError("create_preprocessing(resize=True): no frame")
+        for i, f in enumerate(frames):
+            if not str(getattr(f, "dtype", "")).endswith("uint8"):
+                raise ValueError(f"create_preprocessing(resize=True) takes uint8 frames only, frame {i} is "
+                                 f"{getattr(f, 'dtype', type(f).__name__)}: there is no host resize path")
+            if len(f.shape) != 3 or int(f.shape[2]) != n or min(int(v) for v in f.shape) <= 0:
+                raise ValueError(f"frame {i} has shape {tuple(f.shape)}, expected (Hf, Wf, {n})")
+        boxes, box_indices = check_boxes([tuple(int(v) for v in f.shape[:2]) for f in frames], boxes, box_indices)
+        return DeferredInput(frames, mean.astype(np.float32), std.astype(np.float32), resize=_spec(), boxes=boxes,
+                             box_indices=box_indices)
 
     def _images(imgs):
         """a list / tuple of images, each of a size of its own: one DeferredInput over the list"""
@@ -169,18 +221,18 @@ def create_preprocessing(model_name: str, *, in_channels: Optional[int] = None,
                                  f"{getattr(im, 'dtype', type(im).__name__)}: there is no host resize path")
             if len(im.shape) != 3 or int(im.shape[2]) != n or min(int(v) for v in im.shape) <= 0:
                 raise ValueError(f"image {i} of the list has shape {tuple(im.shape)}, expected (Hs, Ws, {n})")
-        spec = (cfg.interpolation, float(cfg.crop_pct), tuple(int(v) for v in cfg.input_size)) + ((True,) if antialias else ())
-        return DeferredInput(list(imgs), mean.astype(np.float32), std.astype(np.float32), resize=spec)
+        return DeferredInput(list(imgs), mean.astype(np.float32), std.astype(np.float32), resize=_spec())
 
-    def _preprocess(img):
+    def _preprocess(img, boxes=None, box_indices=None):
+        if boxes is not None:
+            return _regions(img, boxes, box_indices)
+        if box_indices is not None:
+            raise ValueError("box_indices without boxes")
         if isinstance(img, (list, tuple)) and (len(img) == 0 or hasattr(img[0], "shape")):
             return _images(img)
         if defer and getattr(img, "dtype", None) is not None and str(img.dtype).endswith("uint8"):
             from .model import DeferredInput
-            spec = (cfg.interpolation, float(cfg.crop_pct), tuple(int(v) for v in cfg.input_size)) if resize else None
-            if antialias:
-                spec += (True,)
-            return DeferredInput(img, mean.astype(np.float32), std.astype(np.float32), resize=spec)
+            return DeferredInput(img, mean.astype(np.float32), std.astype(np.float32), resize=_spec() if resize else None)
         if resize:
             raise ValueError("create_preprocessing(resize=True) takes uint8 images only, got "
                              f"{getattr(img, 'dtype', type(img).__name__)}: there is no host resize path")

@@ -73,10 +73,17 @@ class DeferredInput:
     the float32 image the reference's preprocessing would have produced (models/factory.py:165-167).  With a ``resize``
     spec (``create_preprocessing(..., resize=True)``) the pixels may have any spatial size: resize, centre crop and
     normalisation run in one launch (tfimm_hip_preprocess_resize; with ``antialias=True`` tfimm_hip_preprocess_resize_aa) and
-    ``numpy()`` is the same arithmetic on the CPU."""
+    ``numpy()`` is the same arithmetic on the CPU.  With ``boxes`` (``pre(frames, boxes=..., box_indices=...)``) ``data`` is a
+    list of frames and every box ``(y0, x0, y1, x1)`` -- rows ``[y0, y1)``, columns ``[x0, x1)`` of frame ``box_indices[n]`` --
+    is an image of its own: the batch is the boxes, each computed as the slice would be (tfimm_hip_preprocess_regions[_aa],
+    DESIGN.md 3.22)."""
 
-    def __init__(self, data, mean, std, resize=None):
+    def __init__(self, data, mean, std, resize=None, boxes=None, box_indices=None):
         self.data = data
+        #: int32 (N, 4) corners and int32 (N,) frame indices of ``pre(frames, boxes=...)``, already checked against the
+        #: frames (engine/ffi.py check_boxes); None for every other form
+        self.boxes = boxes
+        self.box_indices = box_indices
         self.mean = tuple(float(np.float32(v)) for v in mean)
         self.std = tuple(float(np.float32(v)) for v in std)
         #: ``create_preprocessing(..., resize=True)``: ``(interpolation, crop_pct, input_size)`` of the model config --
@@ -90,10 +97,21 @@ class DeferredInput:
     @property
     def mixed(self) -> bool:
         """a list of images, each of a size of its own (``create_preprocessing(..., resize=True)`` on a list)"""
-        return isinstance(self.data, (list, tuple))
+        return isinstance(self.data, (list, tuple)) and self.boxes is None
+
+    @property
+    def regions(self) -> bool:
+        """boxes inside a list of frames (``pre(frames, boxes=...)``): the batch is the boxes"""
+        return self.boxes is not None
+
+    def slices(self) -> list:
+        """the boxes as views into their frames, in box order: what the list form ``pre([...])`` would be handed"""
+        return [self.data[int(f)][y0:y1, x0:x1] for (y0, x0, y1, x1), f in zip(self.boxes.tolist(), self.box_indices)]
 
     @property
     def shape(self):
+        if self.regions:
+            return (len(self.boxes), None, None, int(self.data[0].shape[2]))
         if self.mixed:
             return (len(self.data), None, None, int(self.data[0].shape[2]))
         return tuple(self.data.shape)
@@ -105,7 +123,10 @@ class DeferredInput:
         horizontal, each sum from 0.0 in tap order; bilinear: TensorFlow's compute_lerp -- then the three operations of
         the normalisation, all in float32.  Downscaling is not antialiased unless the spec says so: then the sums run
         over the span tables of tfimm_hip_resize_spans (``tf.image.resize(..., antialias=True)``), vertical pass first,
-        each sum from 0.0 in tap order, for both methods.  A list of images: the stack of every image's own result."""
+        each sum from 0.0 in tap order, for both methods.  A list of images: the stack of every image's own result; boxes:
+        the stack of every slice's own result."""
+        if self.regions:
+            return np.stack([DeferredInput(im, self.mean, self.std, self.resize).numpy() for im in self.slices()])
         if self.mixed:
             return np.stack([DeferredInput(im, self.mean, self.std, self.resize).numpy() for im in self.data])
         d = self.data
@@ -334,6 +355,8 @@ class Model:
 
     def _run(self, x, want_features: bool, top_k: Optional[int] = None):
         import torch
+        if isinstance(x, DeferredInput) and x.regions:
+            return self._run_regions(x, want_features, top_k)
         xd = self._to_device(x)
         norm = (tuple(x.mean), tuple(x.std)) if isinstance(x, DeferredInput) else None
         if isinstance(xd, list):
@@ -398,14 +421,51 @@ class Model:
         (``Plan.stage_mixed``), then the program is launched or replayed -- the recording reads the plan's buffers, whatever
         they hold.  Only a buffer that had to grow drops the recording.  ``branches`` is not used: a mixed batch runs on one
         branch (same bits, the engine's kernels never mix images)."""
-        import torch
         from ..engine.graph import MIXED
+        return self._run_staged(len(imgs), lambda plan, lo, hi, norm: plan.stage_mixed(imgs[lo:hi], norm), MIXED, "mixed", norm,
+                                resize, want_features, top_k)
+
+    def _run_regions(self, x: "DeferredInput", want_features: bool, top_k: Optional[int] = None):
+        """Boxes inside larger frames, ``pre(frames, boxes=...)``: ``_run_mixed`` with the boxes as the
+        batch.  The keys carry ``("src", "regions")``, so every set of frames, frame sizes and boxes meets the same plan and
+        the same recording per (model, N, precision); per chunk of boxes the plan uploads the frames the chunk names, once
+        each, with records and tables (``Plan.stage_regions``).  Runs on one branch, as a mixed batch does."""
+        import torch
+        from ..engine.graph import REGIONS
+        frames = [np.ascontiguousarray(f.cpu().numpy() if hasattr(f, "cpu") else f) for f in x.data]
+        if x.resize is None or not frames or len(x.mean) != self.cfg.in_channels or any(
+                f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != self.cfg.in_channels or f.size == 0 for f in frames):
+            raise ValueError(f"{self.name}: expected uint8 frames (Hf, Wf, {self.cfg.in_channels}) with a resize spec, got "
+                             f"shapes {[tuple(f.shape) for f in frames]}")
+        if not torch.cuda.is_available():
+            raise RuntimeError("tfimm (MI355X engine) needs a ROCm GPU: no CPU execution path exists.")
+        boxes, idx = x.boxes, x.box_indices
+        if len(x.resize) > 3 and (self.micro_batch or len(boxes)) < len(boxes):
+            # several chunks: the antialias domain of EVERY box before the first chunk is staged or launched, by the box's own
+            # number (a single chunk is refused by stage_regions itself, before it touches the plan)
+            from ..engine import ffi
+            from .factory import resize_geometry
+            method, crop_pct, size = x.resize[:3]
+            for n, (y0, x0, y1, x1) in enumerate(boxes.tolist()):
+                Rh, Rw = resize_geometry((y1 - y0, x1 - x0), size, crop_pct)[:2]
+                T = max(ffi.resize_span_taps(y1 - y0, Rh, method), ffi.resize_span_taps(x1 - x0, Rw, method))
+                if T > ffi.RESIZE_AA_MAX_TAPS:
+                    raise ValueError(f"{self.name}: antialiased {method} resize: box {n} ({y1 - y0} x {x1 - x0} -> {Rh} x {Rw}) "
+                                     f"needs {T} taps per output pixel, more than TFIMM_RESIZE_AA_MAX_TAPS = "
+                                     f"{ffi.RESIZE_AA_MAX_TAPS}: the box is too large for the device resize")
+        return self._run_staged(len(boxes), lambda plan, lo, hi, norm: plan.stage_regions(frames, boxes[lo:hi], idx[lo:hi], norm),
+                                REGIONS, "regions", (tuple(x.mean), tuple(x.std)), x.resize, want_features, top_k)
+
+    def _run_staged(self, B, stage, marker, tag, norm, resize, want_features: bool, top_k: Optional[int] = None):
+        """What ``_run_mixed`` and ``_run_regions`` share: a batch of ``B`` whose input step reads buffers the plan owns.
+        ``stage(plan, lo, hi, norm)`` uploads members [lo, hi) and returns True when a buffer grew; ``marker`` is what
+        ``Plan.run`` / ``Plan.capture`` take in place of an input tensor; ``tag`` names the form in the keys."""
+        import torch
         method, crop_pct, (H, W) = resize[:3]
         aa = len(resize) > 3
         norm = norm + ((method, crop_pct) + ((True,) if aa else ()),)
-        src = (("src", "mixed") + (("antialias",) if aa else ()),) + self._topk_key(top_k)
+        src = (("src", tag) + (("antialias",) if aa else ()),) + self._topk_key(top_k)
         prog = self.program(H, W, want_features, top_k)
-        B = len(imgs)
         mb = min(self.micro_batch or B, B)
         results: Dict[str, list] = {k: [] for k in prog.outputs}
         for start in range(0, B, mb):
@@ -415,16 +475,16 @@ class Model:
             if plan is None:
                 plan = self._plans[key] = prog.make_plan(nb)
             gkey = key + ("torch.uint8", norm)
-            if plan.stage_mixed(imgs[start:start + nb], norm):
+            if stage(plan, start, start + nb, norm):
                 self._captured.pop(gkey, None)        # a buffer grew: the recording points at the old one
             cap = self._captured.get(gkey)
             if cap is None and self._plan_uses.get(gkey, 0) >= 1 and os.environ.get("TFIMM_NO_GRAPH", "0") != "1":
-                cap = self._captured[gkey] = plan.capture(MIXED, norm)
+                cap = self._captured[gkey] = plan.capture(marker, norm)
             self._plan_uses[gkey] = self._plan_uses.get(gkey, 0) + 1
             if cap is not None:
                 cap.replay()
             else:
-                plan.run(MIXED, norm=norm)
+                plan.run(marker, norm=norm)
             for name, t in prog.outputs.items():
                 results[name].append(plan.tensor_view(t).clone())
         out = {}
@@ -507,6 +567,13 @@ class Model:
         out = self._run(x, False, top_k=int(k))
         return TopK(Tensor(out["topk_indices"]), Tensor(out["topk_values"]), Tensor(out["topk_probs"]))
 
+    @staticmethod
+    def _batch_of(x) -> int:
+        """images in ``x``, whatever ``__call__`` takes: the members of a list, the BOXES of ``pre(frames, boxes=...)``"""
+        if isinstance(x, DeferredInput):
+            return int(x.shape[0])
+        return len(x) if isinstance(x, (list, tuple)) else int(x.shape[0])
+
     def _check_evaluate(self, x, labels, meter):
         """``ValueError`` for what ``evaluate`` cannot score, before any device work; returns the checked labels as the
         callable that uploads them"""
@@ -524,7 +591,7 @@ class Model:
         if meter is not None and meter.nb_classes != n:
             raise ValueError(f"{self.name}: the meter counts {meter.nb_classes} classes, the model has nb_classes = {n}")
         from .meter import _labels
-        batch = len(x.data) if isinstance(x, DeferredInput) and x.mixed else len(x) if isinstance(x, (list, tuple)) else x.shape[0]
+        batch = self._batch_of(x)
         return _labels(labels, int(batch), f"{self.name}: evaluate")
 
     def evaluate(self, x, labels, meter=None, training: bool = False):
@@ -575,7 +642,7 @@ class Model:
             heads = self.program().outputs["logits"].C // n          # (lowering is host work)
             if heads != 1:
                 raise ValueError(f"{self.name}: the logits hold {heads} heads per image; fit_head fits one")
-        batch = len(x.data) if isinstance(x, DeferredInput) and x.mixed else len(x) if isinstance(x, (list, tuple)) else x.shape[0]
+        batch = self._batch_of(x)
         labels = _labels(labels, int(batch), f"{self.name}: fit_head")
         return probe.step(self._head_input(x), labels)
 
