@@ -1015,6 +1015,37 @@ typedef struct tfimm_head_update_desc {
 } tfimm_head_update_desc;
 TFIMM_API int tfimm_hip_head_update(const tfimm_head_update_desc* d, void* stream);
 
+/* tfimm_hip_distill_grad (csrc/distill.hip; the CPU restatement is tests/distill_ref.py): the loss of the
+ * reference's DistillationProblem behind a student's embedding head and its gradient with respect to the student's
+ * embeddings, as the bf16 rows tfimm_hip_head_update takes for g -- the launch between tfimm_hip_gemm and
+ * tfimm_hip_head_update in a step of tfimm.EmbeddingProbe.  Per row b, student s[b][0:E] and teacher t[b][0:E], float32:
+ *   inv_s = 1 / sqrt(max(sum_e s_e^2, 1e-12)),  u = s * inv_s ;  inv_t and v from t alike (tfimm_hip_l2_normalize's rule,
+ *   IEEE square root and division)
+ *   cosine[b] = sum_e u_e v_e, formed as c = ((sum_e s_e t_e) * inv_s) * inv_t, under either value of `normalize`
+ *   normalize == 1:  loss[b] = sum_e (u_e - v_e)^2 ;  d loss / d s_e = 2 * inv_s * (c * u_e - v_e).
+ *                    A row with sum s^2 < 1e-12 is under the clamp: inv_s is the constant 1e6 there and the derivative is the
+ *                    clamp's own, 2 * inv_s * (u_e - v_e).
+ *   normalize == 0:  loss[b] = sum_e (s_e - t_e)^2 ;  d loss / d s_e = 2 * (s_e - t_e)
+ *   grad  bf16 [B][ldg]   grad[b][e] = bf16_rne(d loss / d s_e) for e < E; columns [E, ldg) are never written
+ *   loss, cosine  float32 [B]
+ *   valid int32 [B]       0: train on the row; -1: ignore it.  An ignored row gets +0.0 in every gradient column, loss = 0
+ *                         and cosine = 0, and its s and t are not read.  The same array is handed to tfimm_hip_head_update
+ *                         as `labels` with C = E, and the division by the number of trained rows is done THERE, not here;
+ *                         so that the two launches can never disagree about a row, this one trains on exactly the rows
+ *                         head_update counts: valid[b] in [0, E).
+ * One wave per row; each of the four sums of a row is formed in a fixed order (per lane over its columns ascending, then a
+ * six-step butterfly) that depends on E alone -- not on B, not on the workgroup that holds the row, not on the alignment of
+ * s and t.  Asynchronous on `stream` and capturable, no allocation, no atomics, 64-bit offsets, bit-reproducible.
+ * Non-finite inputs are not detected: they propagate into the row's outputs (and from there into the weights).
+ * TFIMM_EINVAL before any launch, naming the argument: a NULL pointer; s / t / valid / loss / cosine not 4-byte aligned; grad
+ * not 16-byte aligned; ld_s < E; ld_t < E; ldg < E or ldg % 8 != 0; E outside [1, TFIMM_DISTILL_MAX_E]; B < 0; normalize
+ * outside {0, 1}.  B == 0 returns 0 and launches nothing.  Float32 under every precision mode: no tfimm_hip_ref_* twin.
+ * Replaces, in a caller of the reference (tfimm/train/problems/distillation.py): the loss of train_step_inner and its
+ * backward pass down to the embeddings. */
+#define TFIMM_DISTILL_MAX_E 4096
+TFIMM_API int tfimm_hip_distill_grad(const float* s, int64_t ld_s, const float* t, int64_t ld_t, int B, int E, const int32_t* valid,
+                                     int normalize, void* grad, int64_t ldg, float* loss, float* cosine, void* stream);
+
 /* =======================================================================================
  * EMBEDDING END (csrc/embed.hip): row normalisation of float32 embeddings, and the search of a bf16 gallery
  * ======================================================================================= */

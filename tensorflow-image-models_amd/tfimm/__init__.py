@@ -11,7 +11,7 @@ from .models.gallery import Gallery, Matches  # noqa: F401
 from .models.meter import Meter, MeterResult, MeterState, Scores, score  # noqa: F401
 from .models.model import Tensor, TopK  # noqa: F401
 from .models.registry import list_models  # noqa: F401
-from .train import LinearProbe, StepResult  # noqa: F401
+from .train import DistillResult, EmbeddingProbe, LinearProbe, StepResult  # noqa: F401
 from .utils import (  # noqa: F401
     cached_model_path,
     clear_model_cache,

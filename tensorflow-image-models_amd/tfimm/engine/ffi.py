@@ -265,6 +265,8 @@ SYMBOLS = {
     # the head fit (csrc/head_fit.hip): logits, ld, B, N, labels, grad, ldg, loss, pred | descriptor
     "tfimm_hip_softmax_grad": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tfimm_hip_head_update": (_i, [C.POINTER(HeadUpdateDesc), _vp]),
+    # the distillation gradient (csrc/distill.hip): s, ld_s, t, ld_t, B, E, valid, normalize, grad, ldg, loss, cosine
+    "tfimm_hip_distill_grad": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
     # the embedding end (csrc/embed.hip): x, ld_x, B, E, y, ld_y | B, N, E, k, chunk |
     # q, ld_q, B, g, ld_g, N, E, k, chunk, scores, indices, workspace, workspace_bytes
     "tfimm_hip_l2_normalize": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
@@ -400,6 +402,7 @@ SCORE_RANK_BINS, SCORE_STATE_WORDS = 65, 70
 # include/tfimm_hip.h: the optimizers and the domain of tfimm_hip_head_update
 HEAD_SGD, HEAD_ADAM = 0, 1
 HEAD_MAX_D, HEAD_MAX_C, HEAD_MAX_B = 8192, 32768, 65535
+DISTILL_MAX_E = 4096              # tfimm_hip_distill_grad: columns of an embedding row
 
 # include/tfimm_hip.h: the domain of tfimm_hip_embed_search (E a multiple of 16; the gallery row pitch a multiple of 8 elements)
 EMBED_MIN_E, EMBED_MAX_E, EMBED_MAX_K = 16, 2048, 64

@@ -646,6 +646,18 @@ class Model:
         labels = _labels(labels, int(batch), f"{self.name}: fit_head")
         return probe.step(self._head_input(x), labels)
 
+    def distill_head(self, x, teacher, probe, valid=None, training: bool = False):
+        """One step of a ``tfimm.EmbeddingProbe`` on this model's frozen features towards a teacher's embeddings:
+        ``probe.step(_head_input(x), teacher, valid)``.  Takes everything ``__call__`` takes; ``teacher`` is (B, embed_dim),
+        typically another model's output for the same images (``teacher_model(pre_t(img))``), and is checked against the
+        batch of ``x`` before any device work.  The model's weights, programs, plans and recordings are not touched
+        (``probe.install(embedding_model)`` hands the trained head over).  Returns ``DistillResult(loss, cosine)``, each (B,),
+        without waiting for the device."""
+        if training:
+            raise NotImplementedError("This engine implements the inference forward path only (training=False).")
+        targets = probe._targets(teacher, valid, int(self._batch_of(x)), f"{self.name}: distill_head")
+        return probe.step(self._head_input(x), targets)
+
     def forward_features(self, x, training: bool = False, return_features: bool = False):
         if training:
             raise NotImplementedError("This engine implements the inference forward path only (training=False).")
