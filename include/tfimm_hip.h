@@ -1086,6 +1086,68 @@ TFIMM_API int tfimm_hip_embed_search(const float* q, int64_t ld_q, int B, const 
                                      float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* =======================================================================================
+ * KNN END (csrc/knn.hip; the CPU restatement of the rule is tests/knn_ref.py): the matches of a gallery
+ * search turned into classes through a label per gallery row, in one launch behind tfimm_hip_embed_search.
+ * Both entry points read, per query b, the candidates indices[b][0:k] (int32) and scores[b][0:k] (float32) of rows with
+ * pitch ld -- columns >= k are never read -- the labels glabels[0:N] (int32) of the gallery rows and, when exclude is not
+ * NULL, exclude[b] (int32; a value no candidate holds, -1 for one, excludes nothing).  Candidate j is VALID when
+ * 0 <= indices[j] < N, indices[j] != exclude[b] and glabels[indices[j]] >= 0 (tfimm_hip_knn_score: and < nb_classes); no
+ * label is read for an index outside [0, N); a candidate that is not valid contributes nothing.  Specified for finite scores.
+ * One wave per query, four queries per workgroup of 256 threads, lane j owns candidate j; registers and cross-lane operations
+ * only: no LDS, no float atomics, no allocation, capturable, 64-bit offsets.  Every sum runs over the candidates in ascending
+ * j: results are bit-reproducible and a query's outputs do not depend on B.  Float32 under every precision mode: no
+ * tfimm_hip_ref_* twin.
+ * TFIMM_EINVAL before any launch, with a message naming the argument: a NULL required pointer; a pointer that is not 4-byte
+ * (state, per_class: 8-byte) aligned; k outside [1, TFIMM_KNN_MAX_K]; ld < k; N < 1; B < 0; inv_temperature negative, NaN or
+ * infinite; and what each entry point adds below.  B == 0 returns 0 and launches nothing.
+ * ======================================================================================= */
+#define TFIMM_KNN_MAX_K TFIMM_EMBED_MAX_K
+#define TFIMM_KNN_MAX_TOP 64
+#define TFIMM_KNN_SUM 0
+#define TFIMM_KNN_MAX 1
+
+/* tfimm_hip_knn_vote: per query the `top` best classes among its valid candidates.
+ *   reduce == TFIMM_KNN_SUM: m = the largest valid score, w_j = expf((s_j - m) * inv_temperature) -- one float32
+ *     subtraction, one float32 product, expf; inv_temperature == 0 makes every weight exactly 1, the majority vote --
+ *     value[c] = the float32 sum of w_j over the valid candidates of class c in ascending j, count[c] their number,
+ *     total[b] = the float32 sum of w_j over all valid candidates in ascending j.
+ *   reduce == TFIMM_KNN_MAX: value[c] = the largest raw score among the candidates of class c (-0.0 == +0.0; of equal maxima
+ *     the one at the lowest j is written), count[c] as above, total[b] = +0.0; inv_temperature is not used.  When the
+ *     candidates are the k best rows of the whole gallery in the search's order, the classes of this list are exactly the top
+ *     distinct identities of the gallery: an identity absent from the list has its best row below the k-th score.
+ *   classes int32 [B][top], values float32 [B][top], counts int32 [B][top]: the classes by value descending, equal values by
+ *     ascending class; slots beyond the number of distinct classes hold class -1, value +0.0, count 0.  total float32 [B].
+ * Labels are any non-negative int32.  Also refused: NULL classes / values / counts / total; reduce not one of the two;
+ * top outside [1, TFIMM_KNN_MAX_TOP].
+ * Replaces, in a caller of the search: indices to the host, the label lookup and the vote (or the de-duplication) there. */
+TFIMM_API int tfimm_hip_knn_vote(const int32_t* indices, const float* scores, int64_t ld, int B, int k, const int32_t* glabels,
+                                 int N, const int32_t* exclude, float inv_temperature, int reduce, int top, int32_t* classes,
+                                 float* values, int32_t* counts, float* total, void* stream);
+
+/* tfimm_hip_knn_score: the TFIMM_KNN_SUM vote of each query scored against its true label labels[b], as tfimm_hip_score
+ * scores a row of logits.  With v[0:nb_classes) the dense vote vector (v[c] = value[c] for voted classes, 0 otherwise):
+ *   pred  int32    the first class in the order (value descending, equal values by ascending class): tfimm_hip_score's pred
+ *                  on the row v; 0 when no candidate is valid
+ *   rank  int32    the number of classes that beat class y in that order: tfimm_hip_score's rank on the row v.  An unvoted
+ *                  class ties with a voted class whose weights underflowed to 0.  Counted from the (at most k) voted classes
+ *                  alone -- those that beat y, and, when v[y] == 0, y minus the voted classes below y -- never by a loop over
+ *                  nb_classes, which may be as large as 2^31 - 1.  With no valid candidate rank = y.
+ *   prob  float32  v[y] / total, correctly rounded; 0 when total == 0
+ *   loss  float32  0 - logf(prob): +inf at prob == 0 (nobody voted for the true class), +0.0 at prob == 1
+ * y == TFIMM_SCORE_IGNORE is not scored: loss = 0, prob = 0, rank = -1; any other y outside [0, nb_classes) likewise with
+ * rank = -2.  pred is written for every row.
+ * state / per_class / confusion: the accumulators of tfimm_hip_score with N = nb_classes -- its layouts, its constants, its
+ * integer atomic adds issued by one lane per query -- so that one meter can be fed by both; a +inf loss is counted in
+ * TFIMM_SCORE_LOSS_EXCLUDED by that function's rule.  Each may be NULL.
+ * Also refused: NULL labels / loss / rank / pred / prob; nb_classes < 1; confusion with nb_classes >
+ * TFIMM_SCORE_MAX_CONFUSION_N.
+ * Replaces, in a kNN evaluation of an embedding: indices to the host, the vote and the accuracy counters there. */
+TFIMM_API int tfimm_hip_knn_score(const int32_t* indices, const float* scores, int64_t ld, int B, int k, const int32_t* glabels,
+                                  int N, const int32_t* exclude, float inv_temperature, int nb_classes, const int32_t* labels,
+                                  float* loss, int32_t* rank, int32_t* pred, float* prob, int64_t* state, int64_t* per_class,
+                                  uint32_t* confusion, void* stream);
+
+/* =======================================================================================
  * LOW-RANK ADAPTER (csrc/lora.hip): the LoRA term of a Dense layer as an op of its own
  * ======================================================================================= */
 

@@ -272,6 +272,10 @@ SYMBOLS = {
     "tfimm_hip_l2_normalize": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
     "tfimm_hip_embed_search_workspace": (_i64, [_i, _i, _i, _i, _i]),
     "tfimm_hip_embed_search": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    # the kNN end (csrc/knn.hip): indices, scores, ld, B, k, glabels, N, exclude, inv_temperature, then
+    # reduce, top, classes, values, counts, total | nb_classes, labels, loss, rank, pred, prob, state, per_class, confusion
+    "tfimm_hip_knn_vote": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "tfimm_hip_knn_score": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # the low-rank adapter term (csrc/lora.hip)
     "tfimm_hip_lora_delta": (_i, [C.POINTER(LoraDesc), _vp]),
     # program-level entry points (csrc/plan.hip): a serialised plan (graph.Plan.export) run without Python host logic
@@ -407,6 +411,8 @@ DISTILL_MAX_E = 4096              # tfimm_hip_distill_grad: columns of an embedd
 # include/tfimm_hip.h: the domain of tfimm_hip_embed_search (E a multiple of 16; the gallery row pitch a multiple of 8 elements)
 EMBED_MIN_E, EMBED_MAX_E, EMBED_MAX_K = 16, 2048, 64
 EMBED_MAX_B = 65535 * 32          # queries per call: tiles of 32 are one grid dimension
+# include/tfimm_hip.h: the domain of tfimm_hip_knn_vote / tfimm_hip_knn_score (one lane per candidate and per slot of the list)
+KNN_MAX_K, KNN_MAX_TOP, KNN_SUM, KNN_MAX = EMBED_MAX_K, 64, 0, 1
 
 
 def resize_span_taps(n_in: int, n_resized: int, method: str) -> int:

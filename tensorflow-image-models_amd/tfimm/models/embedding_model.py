@@ -172,3 +172,29 @@ class EmbeddingModel(Model):
             raise ValueError(f"{self.name}: embeddings are a map {emb.shape} (the backbone's forward_features is one): a gallery "
                              f"holds one row per image, pool the map first")
         return gallery.search(emb, k)
+
+    def _embeddings_for(self, x, gallery):
+        emb = self(x)
+        if len(emb.shape) != 2:
+            raise ValueError(f"{self.name}: embeddings are a map {emb.shape} (the backbone's forward_features is one): a gallery "
+                             f"holds one row per image, pool the map first")
+        return emb
+
+    def classify(self, x, gallery, k: int = 20, temperature=0.07, top: int = 5, reduce: str = "sum", exclude=None):
+        """``gallery.classify(model(x), ...)``: the classes of the images from their ``k`` nearest labelled gallery rows --
+        ``Votes(classes, values, counts, total)`` -- behind the model's recording on the same stream; neither embeddings
+        nor matches leave the device.  Every argument is checked before the forward pass runs."""
+        if gallery.dim != self.embed_dim:
+            raise ValueError(f"{self.name}: embeddings have {self.embed_dim} columns, the gallery holds rows of {gallery.dim}")
+        run = gallery._plan_classify(f"{self.name}: classify", int(self._batch_of(x)), k, temperature, top, reduce, exclude)
+        return run(self._embeddings_for(x, gallery))
+
+    def evaluate_knn(self, x, labels, gallery, k: int = 20, temperature=0.07, meter=None, nb_classes=None, exclude=None):
+        """``gallery.evaluate(model(x), labels, ...)``: the kNN probe of this embedding -- ``Scores(loss, rank, pred, prob)``
+        of the weighted vote against the true labels, added to ``meter`` on the device (what ``LinearProbe`` is to a
+        classifier head, without any training).  Every argument is checked before the forward pass runs."""
+        if gallery.dim != self.embed_dim:
+            raise ValueError(f"{self.name}: embeddings have {self.embed_dim} columns, the gallery holds rows of {gallery.dim}")
+        run = gallery._plan_evaluate(f"{self.name}: evaluate_knn", int(self._batch_of(x)), labels, k, temperature, meter,
+                                     nb_classes, exclude)
+        return run(self._embeddings_for(x, gallery))

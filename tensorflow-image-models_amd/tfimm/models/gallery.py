@@ -1,5 +1,6 @@
 """``Gallery``: embeddings to search, resident on the device as bf16, and the fused search over them
-(tfimm_hip_embed_search, csrc/embed.hip)."""
+(tfimm_hip_embed_search, csrc/embed.hip); with a label per row, the matches turned into classes and
+scored on the device (tfimm_hip_knn_vote / tfimm_hip_knn_score, csrc/knn.hip)."""
 import ctypes as C
 from collections import namedtuple
 
@@ -11,13 +12,45 @@ from .model import Tensor
 #: by score descending, equal scores by ascending row
 Matches = namedtuple("Matches", ["indices", "scores"])
 
+#: what ``Gallery.vote`` / ``Gallery.classify`` return: ``Tensor`` on the device -- int32 classes, float32 values and int32
+#: counts, each (B, top), by value descending, equal values by ascending class, empty slots (-1, 0, 0); float32 total (B,)
+Votes = namedtuple("Votes", ["classes", "values", "counts", "total"])
+
+_REDUCE = ("sum", "max")          # TFIMM_KNN_SUM, TFIMM_KNN_MAX
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _row_labels(labels, n, what):
+    """``labels`` of ``n`` gallery rows in the forms ``meter._labels`` takes.  Host labels are validated -- -1: the row never
+    votes; below -1 or above 2^31 - 1: ``ValueError`` --, device labels are not looked at (no synchronisation).  Returns the
+    callable that does the device part."""
+    import torch
+    from .meter import _labels
+    upload = _labels(labels, n, what)
+    y = labels.torch() if isinstance(labels, Tensor) else labels
+    if not (isinstance(y, torch.Tensor) and y.is_cuda):
+        a = y.numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+        if a.size and (int(a.min()) < -1 or int(a.max()) > 2 ** 31 - 1):
+            raise ValueError(f"{what}: labels: a gallery label is a class in [0, 2^31 - 1] or -1 (the row never votes), got "
+                             f"values in [{int(a.min())}, {int(a.max())}]")
+    return upload
+
 
 class Gallery:
     """``Gallery(dim, capacity=0)``: a growing (N, dim) matrix of bf16 rows in device memory with a 16-byte-aligned row
     pitch.  ``add`` appends float32 rows (rounded to nearest even), ``search`` returns for every query the ``k`` rows with
     the largest inner product -- scores and top-k in one pass over the gallery, the (B, N) score matrix never exists.  With
     L2-normalised rows and queries (``EmbeddingModel(..., normalize=True)``) the score is the cosine similarity.  Rows are
-    never removed or updated; there is no id / label table: a row's index is its identity."""
+    never removed or updated.
+
+    Without labels a row's index is its identity.  ``add(x, labels)`` on an empty gallery makes it a LABELLED one: an int32
+    label per row lives next to the rows on the device (several rows per person, hundreds per class), every later ``add``
+    needs labels, and one more launch behind the search turns the matches into classes: ``vote`` / ``classify`` -- a weighted
+    vote, or the best row per identity -- and ``evaluate``, which scores a labelled batch of queries into a ``tfimm.Meter``:
+    the kNN probe of an embedding, with no host trip per batch."""
 
     def __init__(self, dim: int, capacity: int = 0):
         from ..engine import ffi
@@ -33,6 +66,8 @@ class Gallery:
         self._n = 0
         self._buf = None                              # torch.bfloat16 (capacity, pitch), allocated on the first add
         self._work = {}                               # (B, k) -> workspace of the search (uint8)
+        self._labelled = False
+        self._lab = None                              # torch.int32 (capacity,), a labelled gallery's label per row
 
     def __len__(self) -> int:
         return self._n
@@ -41,9 +76,18 @@ class Gallery:
     def capacity(self) -> int:
         return self._capacity
 
+    @property
+    def labelled(self) -> bool:
+        """whether the rows carry labels (``add(x, labels)`` on the empty gallery)"""
+        return self._labelled
+
     def _rows(self, x, what: str):
         """``x`` as a float32 device tensor (n, dim): a ``Tensor`` (or torch tensor) on the GPU stays where it is, host data
         -- an array, a torch tensor on the CPU -- is uploaded"""
+        return self._upload_rows(self._check_rows(x, what))
+
+    def _check_rows(self, x, what: str):
+        """the ``ValueError`` part of ``_rows``: ``x`` as the (n, dim) float32 array or torch tensor it is, not moved"""
         import torch
         if isinstance(x, Tensor):
             t = x.torch()
@@ -55,6 +99,11 @@ class Gallery:
             raise ValueError(f"Gallery.{what}: expected float32, got {t.dtype}")
         if t.ndim != 2 or t.shape[1] != self.dim:
             raise ValueError(f"Gallery.{what}: expected shape (n, {self.dim}), got {tuple(t.shape)}")
+        return t
+
+    @staticmethod
+    def _upload_rows(t):
+        import torch
         if isinstance(t, np.ndarray) or not t.is_cuda:
             # host data -- an array, or a torch tensor that is not on the GPU -- is uploaded; the kernel never sees a host pointer
             if not torch.cuda.is_available():
@@ -62,14 +111,32 @@ class Gallery:
             t = (torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t).to("cuda", non_blocking=True)
         return t
 
-    def add(self, x) -> range:
+    def add(self, x, labels=None) -> range:
         """Append the rows of ``x`` -- a ``Tensor`` (it stays on the device) or an array, float32 (n, dim) -- rounded to bf16
-        by round-to-nearest-even; returns the ``range`` of their indices."""
-        import torch
-        t = self._rows(x, "add")
+        by round-to-nearest-even; returns the ``range`` of their indices.  ``labels``: one class per row -- a list, an integer
+        array or a torch int32 / int64 tensor on either side, (n,).  The first ``add`` with labels, on an empty gallery,
+        makes the gallery a labelled one; from then on every ``add`` needs them, and an unlabelled gallery that holds rows
+        takes none.  -1 marks a row that is searched but never votes; host labels below -1 or above 2^31 - 1 are refused,
+        device labels are not looked at (no synchronisation; a negative one never votes)."""
+        t = self._check_rows(x, "add")
         n = int(t.shape[0])
         if self._n + n >= 2 ** 31:
             raise ValueError("Gallery: at most 2^31 - 1 rows")
+        up_labels = None
+        if labels is None:
+            if self._labelled:
+                raise ValueError(f"Gallery.add: this gallery is labelled: {n} rows need {n} labels")
+        else:
+            if not self._labelled and self._n:
+                raise ValueError(f"Gallery.add: labels for a gallery that holds {self._n} rows without: a gallery is labelled "
+                                 f"from its first row on, or not at all")
+            up_labels = _row_labels(labels, n, "Gallery.add")
+        return self._store(t, up_labels, n)
+
+    def _store(self, t, up_labels, n: int) -> range:
+        """the device part of ``add``"""
+        import torch
+        t = self._upload_rows(t)
         if self._buf is None or self._n + n > self._capacity:
             cap = max(self._n + n, 2 * self._capacity if self._buf is not None else self._capacity, 1)
             buf = torch.zeros((cap, self.pitch), dtype=torch.bfloat16, device=t.device)
@@ -77,8 +144,44 @@ class Gallery:
                 buf[:self._n].copy_(self._buf[:self._n])
             self._buf, self._capacity = buf, cap
         self._buf[self._n:self._n + n, :self.dim].copy_(t)           # float32 -> bf16: nearest even
+        if up_labels is not None:
+            self._labelled = True
+            if self._lab is None or self._lab.shape[0] < self._capacity:     # grows with the rows
+                lab = torch.full((self._capacity,), -1, dtype=torch.int32, device=t.device)
+                if self._n:
+                    lab[:self._n].copy_(self._lab[:self._n])
+                self._lab = lab
+            self._lab[self._n:self._n + n].copy_(up_labels())
         first, self._n = self._n, self._n + n
         return range(first, self._n)
+
+    def labels(self) -> np.ndarray:
+        """the labels of the rows, numpy int32 (len,) (one device -> host copy)"""
+        self._need_labels("Gallery.labels")
+        if self._lab is None:
+            return np.zeros(0, np.int32)
+        return self._lab[:self._n].cpu().numpy()
+
+    def labels_of(self, indices) -> Tensor:
+        """the labels of the rows ``indices`` -- a ``Tensor`` (``Matches.indices``), a torch tensor or an integer array of any
+        shape -- as an int32 ``Tensor`` of that shape on the device: a torch gather, no kernel of ours.  The entries are not
+        looked at on the host; one outside [0, len) gives -1."""
+        import torch
+        self._need_labels("Gallery.labels_of")
+        i = indices.torch() if isinstance(indices, Tensor) else indices
+        if not isinstance(i, torch.Tensor):
+            i = torch.from_numpy(np.ascontiguousarray(np.asarray(i)))
+        if i.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"Gallery.labels_of: indices: expected int32 or int64, got {i.dtype}")
+        if not self._n:
+            raise ValueError("Gallery.labels_of: the gallery is empty")
+        i = i.to(self._lab.device).long()
+        inside = (i >= 0) & (i < self._n)
+        return Tensor(torch.where(inside, self._lab[i.clamp(0, self._n - 1)], torch.full_like(i, -1, dtype=torch.int32)))
+
+    def _need_labels(self, what: str) -> None:
+        if not self._labelled:
+            raise ValueError(f"{what}: this gallery has no labels (add(x, labels) on the empty gallery makes it a labelled one)")
 
     def numpy(self) -> np.ndarray:
         """the stored rows widened to float32, (len, dim)"""
@@ -120,3 +223,178 @@ class Gallery:
                                                  int(chunk), scores.data_ptr(), indices.data_ptr(), work.data_ptr(),
                                                  work.numel(), st), "tfimm_hip_embed_search")
         return Matches(Tensor(indices), Tensor(scores))
+
+    # -- the kNN end: matches -> classes (csrc/knn.hip) ----------------------------------------------------------------------
+    @staticmethod
+    def _vote_args(what, temperature, top, reduce):
+        """(inv_temperature, reduce id) of checked arguments"""
+        from ..engine import ffi
+        if reduce not in _REDUCE:
+            raise ValueError(f"{what}: reduce = {reduce!r}, must be 'sum' or 'max'")
+        if not _is_int(top) or not 1 <= top <= ffi.KNN_MAX_TOP:
+            raise ValueError(f"{what}: top = {top!r}, must be an integer in [1, TFIMM_KNN_MAX_TOP = {ffi.KNN_MAX_TOP}]")
+        inv_t = 0.0                                      # temperature=None: every weight is 1, the majority vote
+        if reduce == "sum" and temperature is not None:
+            ok = not isinstance(temperature, bool) and isinstance(temperature, (int, float, np.integer, np.floating))
+            if ok:
+                with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+                    inv_t = float(np.float32(1.0) / np.float32(temperature))
+            if not ok or not temperature > 0 or not np.isfinite(inv_t):
+                raise ValueError(f"{what}: temperature = {temperature!r}, must be a positive number whose inverse is a finite "
+                                 f"float32, or None for the majority vote")
+        return inv_t, _REDUCE.index(reduce)
+
+    def _knn_k(self, what, k, exclude) -> int:
+        """the ``k`` the search is asked for: one more with ``exclude``, whose row takes a place among the matches"""
+        from ..engine import ffi
+        if not _is_int(k):
+            raise ValueError(f"{what}: k must be an integer, got {k!r}")
+        extra = 0 if exclude is None else 1
+        if k < 1 or k + extra > ffi.EMBED_MAX_K or k + extra > self._n:
+            raise ValueError(f"{what}: k = {k}{' (+ 1 for the excluded row)' if extra else ''}, must be in [1, min(len = {self._n}, "
+                             f"TFIMM_EMBED_MAX_K = {ffi.EMBED_MAX_K}){' - 1' if extra else ''}]")
+        return int(k) + extra
+
+    @staticmethod
+    def _exclude(exclude, batch, what):
+        if exclude is None:
+            return None
+        from .meter import _labels
+        try:
+            return _labels(exclude, batch, what)
+        except ValueError as e:
+            raise ValueError(str(e).replace("labels", "exclude")) from None
+
+    def _matches(self, matches, what):
+        """(indices, scores) of a ``Matches`` as the int32 / float32 device tensors (B, k) they must be"""
+        import torch
+        from ..engine import ffi
+        try:
+            i, s = (m.torch() if isinstance(m, Tensor) else m for m in matches)
+            ok = isinstance(i, torch.Tensor) and isinstance(s, torch.Tensor)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what}: matches must be the Matches(indices, scores) of Gallery.search")
+        if i.dtype != torch.int32 or s.dtype != torch.float32 or i.ndim != 2 or i.shape != s.shape:
+            raise ValueError(f"{what}: matches: expected int32 indices and float32 scores of one shape (B, k), got {i.dtype} "
+                             f"{tuple(i.shape)} and {s.dtype} {tuple(s.shape)}")
+        if not 1 <= i.shape[1] <= ffi.KNN_MAX_K:
+            raise ValueError(f"{what}: matches with k = {i.shape[1]}, must be in [1, TFIMM_KNN_MAX_K = {ffi.KNN_MAX_K}]")
+        if not (i.is_cuda and s.is_cuda):
+            raise ValueError(f"{what}: matches must be on the device (what Gallery.search returns)")
+        return i.contiguous(), s.contiguous()
+
+    def _launch_vote(self, i, s, up_exclude, inv_t, reduce, top) -> Votes:
+        """tfimm_hip_knn_vote on the current stream, behind whatever produced the matches there; no synchronisation"""
+        import torch
+        from ..engine import ffi
+        B, k = int(i.shape[0]), int(i.shape[1])
+        dev = i.device
+        classes = torch.empty((B, top), dtype=torch.int32, device=dev)
+        values = torch.empty((B, top), dtype=torch.float32, device=dev)
+        counts = torch.empty((B, top), dtype=torch.int32, device=dev)
+        total = torch.empty(B, dtype=torch.float32, device=dev)
+        if B:
+            ex = None if up_exclude is None else up_exclude()
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            ffi.check(ffi.lib.tfimm_hip_knn_vote(i.data_ptr(), s.data_ptr(), k, B, k, self._lab.data_ptr(), self._n,
+                                                 None if ex is None else ex.data_ptr(), inv_t, reduce, top, classes.data_ptr(),
+                                                 values.data_ptr(), counts.data_ptr(), total.data_ptr(), st), "tfimm_hip_knn_vote")
+        return Votes(Tensor(classes), Tensor(values), Tensor(counts), Tensor(total))
+
+    def vote(self, matches, temperature=0.07, top: int = 5, reduce: str = "sum", exclude=None) -> Votes:
+        """``Votes(classes, values, counts, total)`` of the ``Matches`` of a search of this gallery: per query the ``top``
+        classes among the labels of its matches.  ``reduce="sum"``: a vote weighted by ``exp((score - best) / temperature)``
+        (``temperature=None``: every match counts 1, the majority vote); ``values`` are the classes' sums, ``total`` the sum
+        over all matches, ``values / total`` the shares.  ``reduce="max"``: the best row per identity -- ``values`` are raw
+        scores, ``temperature`` is ignored; the classes are exactly the top distinct identities of the whole gallery (an
+        identity that is missing has its best row below the k-th score).  ``counts``: the matches of each class.  Order: value
+        descending, equal values by ascending class; slots beyond the distinct classes hold (-1, 0, 0).  Rows labelled -1
+        never vote, nor does ``exclude[b]`` -- an int vector (B,), the gallery row query ``b`` must not meet (itself, in a
+        leave-one-out evaluation; -1: none).  One launch (tfimm_hip_knn_vote) on the current stream, no synchronisation."""
+        what = "Gallery.vote"
+        self._need_labels(what)
+        inv_t, red = self._vote_args(what, temperature, top, reduce)
+        if not self._n:
+            raise ValueError(f"{what}: the gallery is empty")
+        i, s = self._matches(matches, what)
+        up_ex = self._exclude(exclude, int(i.shape[0]), what)
+        return self._launch_vote(i, s, up_ex, inv_t, red, int(top))
+
+    def _plan_classify(self, what, batch, k, temperature, top, reduce, exclude, chunk=0):
+        """every ``ValueError`` of ``classify`` for a batch of ``batch`` queries; returns the device part, ``run(q)``"""
+        self._need_labels(what)
+        inv_t, red = self._vote_args(what, temperature, top, reduce)
+        ks = self._knn_k(what, k, exclude)
+        up_ex = self._exclude(exclude, batch, what)
+
+        def run(q) -> Votes:
+            m = self.search(q, ks, chunk)
+            return self._launch_vote(m.indices.torch(), m.scores.torch(), up_ex, inv_t, red, int(top))
+        return run
+
+    def classify(self, q, k: int = 20, temperature=0.07, top: int = 5, reduce: str = "sum", exclude=None, chunk: int = 0) -> Votes:
+        """``vote(search(q, k), ...)``: the classes of float32 queries ``q`` (B, dim) from their ``k`` nearest labelled rows,
+        three launches on the current stream and nothing on the host.  With ``exclude`` the search asks for ``k + 1`` rows
+        (the excluded one takes a place), so ``k <= 63`` and ``k + 1 <= len``: ``classify(rows, exclude=arange(len))``
+        evaluates a gallery against itself, leave-one-out."""
+        t = self._check_rows(q, "classify")
+        return self._plan_classify("Gallery.classify", int(t.shape[0]), k, temperature, top, reduce, exclude, chunk)(q)
+
+    def _plan_evaluate(self, what, batch, labels, k, temperature, meter, nb_classes, exclude):
+        """every ``ValueError`` of ``evaluate`` for a batch of ``batch`` queries; returns the device part, ``run(q)``"""
+        from .meter import Meter, Scores, _labels
+        self._need_labels(what)
+        if meter is not None and not isinstance(meter, Meter):
+            raise ValueError(f"{what}: meter must be a tfimm.Meter, got {type(meter).__name__}")
+        if meter is None and nb_classes is None:
+            raise ValueError(f"{what}: nb_classes is needed: pass it, or a meter that knows it")
+        if nb_classes is not None and (not _is_int(nb_classes) or not 1 <= nb_classes <= 2 ** 31 - 1):
+            raise ValueError(f"{what}: nb_classes = {nb_classes!r}, must be an integer in [1, 2^31 - 1]")
+        if meter is not None and nb_classes is not None and meter.nb_classes != nb_classes:
+            raise ValueError(f"{what}: the meter counts {meter.nb_classes} classes, nb_classes = {nb_classes}")
+        n = int(meter.nb_classes if meter is not None else nb_classes)
+        inv_t, _ = self._vote_args(what, temperature, 1, "sum")
+        ks = self._knn_k(what, k, exclude)
+        up_labels = _labels(labels, batch, what)
+        up_ex = self._exclude(exclude, batch, what)
+
+        def run(q) -> Scores:
+            import torch
+            from ..engine import ffi
+            m = self.search(q, ks)
+            i, s = m.indices.torch(), m.scores.torch()
+            B, dev = int(i.shape[0]), i.device
+            loss = torch.empty(B, dtype=torch.float32, device=dev)
+            rank = torch.empty(B, dtype=torch.int32, device=dev)
+            pred = torch.empty(B, dtype=torch.int32, device=dev)
+            prob = torch.empty(B, dtype=torch.float32, device=dev)
+            if B:
+                y = up_labels()
+                ex = None if up_ex is None else up_ex()
+                acc = (None, None, None)
+                if meter is not None:
+                    if meter._buf is None:
+                        meter._buf = torch.zeros(meter._layout()[2], dtype=torch.int64, device=dev)
+                    acc = meter._views()
+                ptr = [None if t is None else t.data_ptr() for t in acc]
+                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                ffi.check(ffi.lib.tfimm_hip_knn_score(i.data_ptr(), s.data_ptr(), ks, B, ks, self._lab.data_ptr(), self._n,
+                                                      None if ex is None else ex.data_ptr(), inv_t, n, y.data_ptr(),
+                                                      loss.data_ptr(), rank.data_ptr(), pred.data_ptr(), prob.data_ptr(),
+                                                      ptr[0], ptr[1], ptr[2], st), "tfimm_hip_knn_score")
+            return Scores(Tensor(loss), Tensor(rank), Tensor(pred), Tensor(prob))
+        return run
+
+    def evaluate(self, q, labels, k: int = 20, temperature=0.07, meter=None, nb_classes=None, exclude=None):
+        """How good is the embedding: the weighted vote of ``classify(q, k, temperature)`` scored against the true
+        ``labels`` (B,) -- ``Scores(loss, rank, pred, prob)`` as ``tfimm.score`` gives them for logits, with the vote vector
+        in their place: ``pred`` the winning class, ``rank`` the true class's position among all ``nb_classes`` (an unvoted
+        class holds 0 and ties by ascending class), ``prob`` its share of the vote, ``loss = -log(prob)`` (inf when nobody
+        voted for it: the meter counts such a row in ``loss_excluded``).  With a ``tfimm.Meter`` the batch is added to it on
+        the device -- the same meter ``tfimm.score`` feeds; ``nb_classes`` comes from it, or from the argument.  A label of
+        -1 is not scored; gallery rows whose label is not below ``nb_classes`` do not vote.  ``exclude`` as in ``classify``.
+        Three launches on the current stream (tfimm_hip_knn_score behind the search), no synchronisation."""
+        t = self._check_rows(q, "evaluate")
+        return self._plan_evaluate("Gallery.evaluate", int(t.shape[0]), labels, k, temperature, meter, nb_classes, exclude)(q)
