@@ -1148,6 +1148,59 @@ TFIMM_API int tfimm_hip_knn_score(const int32_t* indices, const float* scores, i
                                   uint32_t* confusion, void* stream);
 
 /* =======================================================================================
+ * CLUSTER END (csrc/cluster.hip; the CPU restatement of both rules is tests/cluster_ref.py): the two device
+ * operations of grouping a bf16 gallery -- every row to its best centroid, and the mean of the rows of every group.  The
+ * Lloyd loop, class prototypes and pseudo-labels are host code over them (tfimm.Gallery.assign / prototypes / kmeans).
+ * Both follow the conventions of the embedding and kNN ends: TFIMM_EINVAL before any launch, with a message naming the
+ * argument; 64-bit offsets; no allocation, no float atomics, no scratch memory; capturable and bit-reproducible; float32 /
+ * bf16 under every precision mode: no tfimm_hip_ref_* twin.
+ * ======================================================================================= */
+#define TFIMM_CLUSTER_MAX_C 65536
+#define TFIMM_SEGMENT_RUN 256
+
+/* tfimm_hip_cluster_assign: for each of the N rows of the bf16 gallery g [N][ld_g] (read in place) the best of the C bf16
+ * centroids c [C][ld_c]: s[n][j] = sum_e g[n][e] * c[j][e], accumulated in float32 by the matrix unit;
+ *   assign int32   [N]   the j with the largest s[n][j]; of equal scores the lowest j (-0.0 == +0.0)
+ *   score  float32 [N]   that score
+ * Specified for finite inputs; others do not fault.  One launch: a workgroup owns 128 gallery rows and streams the centroids
+ * through LDS in tiles of 128; the running best of a row stays in registers, the N x C score matrix never exists, a row's 8
+ * bytes are written once.  A score is a function of its row, its centroid and E alone: a row's outputs do not depend on N, on
+ * which rows share a call or on how the centroids are tiled, and a centroid's score does not depend on C.
+ * Limits: E a multiple of 16 in [TFIMM_EMBED_MIN_E, TFIMM_EMBED_MAX_E]; 1 <= C <= TFIMM_CLUSTER_MAX_C; 0 <= N < 2^31;
+ * ld_g, ld_c >= E and multiples of 8 elements; g / c 16-byte aligned; assign / score 4-byte aligned.  N == 0 returns 0 and
+ * launches nothing.
+ * Replaces, in a k-means or nearest-class-mean loop: tf.matmul(gallery, centroids, transpose_b=True) + tf.argmax / reduce_max. */
+TFIMM_API int tfimm_hip_cluster_assign(const void* g, int64_t ld_g, int N, const void* c, int64_t ld_c, int C, int E, int32_t* assign,
+                                       float* score, void* stream);
+
+/* tfimm_hip_segment_mean: the mean of the gallery rows of each of C segments.  Segment c is the list
+ * rows[offsets[c] : offsets[c + 1]] of gallery row indices (rows int32 [M], offsets int32 [C + 1]: a CSR form).
+ *   counts int32   [C]         the number of VALID entries of the segment: those inside [0, N)
+ *   mean   float32 [C][ld_m]   the float32 sum of the segment's valid rows divided by float(count) in one correctly rounded
+ *                              float32 division; an empty segment (or one without a valid entry): +0.0 and counts[c] = 0
+ * Out-of-range input does not fault: an entry of rows outside [0, N) contributes nothing, is not counted, and no gallery row
+ * is read for it; offsets are clamped to [0, M], and a segment whose end is below its begin is empty.  mean and counts are
+ * specified for offsets that ascend from segment to segment (a CSR form); any other content does not fault, but the run slots
+ * of two segments may then coincide and their sums mix.
+ * THE ORDER OF THE ADDITIONS, per column, with R = TFIMM_SEGMENT_RUN: the segment's entries, valid or not, are cut into runs of
+ * R counted from the segment's own begin -- run r holds the entries [begin + r R, min(begin + (r + 1) R, end)).  A run's
+ * partial sum starts at +0.0 and adds the run's valid rows one by one in list order; the segment's sum starts at +0.0 and adds
+ * the partial sums one by one in ascending run order.  Every addition is a single float32 addition.  The order is a function of
+ * the segment's own entries in their list order alone: it does not depend on N, M, C, the other segments or the launch.
+ * Two launches on `stream`: the partial sums of all runs -- the work is split by runs, not by segments, so one long segment
+ * costs what many short ones do -- go to `workspace` (segment c owns the run slots from begin / R + c on; at most M / R + C
+ * slots), then one pass per segment combines them.
+ * Limits: E a multiple of 16 in [TFIMM_EMBED_MIN_E, TFIMM_EMBED_MAX_E]; 1 <= C < 2^31; 0 <= M < 2^31; 0 <= N < 2^31; ld_g >= E
+ * and a multiple of 8 elements; ld_m >= E; g and workspace 16-byte aligned, rows / offsets / mean / counts 4-byte aligned;
+ * rows may be NULL when M == 0; workspace_bytes >= tfimm_hip_segment_mean_workspace(M, C, E), which returns the bytes needed
+ * (TFIMM_EINVAL, negative, for an M, C or E the call would refuse).
+ * Replaces, in a k-means or class-prototype loop: tf.math.unsorted_segment_mean over gathered rows. */
+TFIMM_API int64_t tfimm_hip_segment_mean_workspace(int M, int C, int E);
+TFIMM_API int tfimm_hip_segment_mean(const void* g, int64_t ld_g, int N, int E, const int32_t* rows, int M, const int32_t* offsets,
+                                     int C, float* mean, int64_t ld_m, int32_t* counts, void* workspace, int64_t workspace_bytes,
+                                     void* stream);
+
+/* =======================================================================================
  * LOW-RANK ADAPTER (csrc/lora.hip): the LoRA term of a Dense layer as an op of its own
  * ======================================================================================= */
 

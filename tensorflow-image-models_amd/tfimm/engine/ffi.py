@@ -276,6 +276,11 @@ SYMBOLS = {
     # reduce, top, classes, values, counts, total | nb_classes, labels, loss, rank, pred, prob, state, per_class, confusion
     "tfimm_hip_knn_vote": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "tfimm_hip_knn_score": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the cluster end (csrc/cluster.hip): g, ld_g, N, c, ld_c, C, E, assign, score | M, C, E |
+    # g, ld_g, N, E, rows, M, offsets, C, mean, ld_m, counts, workspace, workspace_bytes
+    "tfimm_hip_cluster_assign": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "tfimm_hip_segment_mean_workspace": (_i64, [_i, _i, _i]),
+    "tfimm_hip_segment_mean": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
     # the low-rank adapter term (csrc/lora.hip)
     "tfimm_hip_lora_delta": (_i, [C.POINTER(LoraDesc), _vp]),
     # program-level entry points (csrc/plan.hip): a serialised plan (graph.Plan.export) run without Python host logic
@@ -413,6 +418,8 @@ EMBED_MIN_E, EMBED_MAX_E, EMBED_MAX_K = 16, 2048, 64
 EMBED_MAX_B = 65535 * 32          # queries per call: tiles of 32 are one grid dimension
 # include/tfimm_hip.h: the domain of tfimm_hip_knn_vote / tfimm_hip_knn_score (one lane per candidate and per slot of the list)
 KNN_MAX_K, KNN_MAX_TOP, KNN_SUM, KNN_MAX = EMBED_MAX_K, 64, 0, 1
+# include/tfimm_hip.h: centroids per tfimm_hip_cluster_assign; entries per run of tfimm_hip_segment_mean's summation rule
+CLUSTER_MAX_C, SEGMENT_RUN = 65536, 256
 
 
 def resize_span_taps(n_in: int, n_resized: int, method: str) -> int:

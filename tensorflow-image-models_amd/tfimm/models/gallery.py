@@ -1,6 +1,8 @@
 """``Gallery``: embeddings to search, resident on the device as bf16, and the fused search over them
 (tfimm_hip_embed_search, csrc/embed.hip); with a label per row, the matches turned into classes and
-scored on the device (tfimm_hip_knn_vote / tfimm_hip_knn_score, csrc/knn.hip)."""
+scored on the device (tfimm_hip_knn_vote / tfimm_hip_knn_score, csrc/knn.hip); and the rows grouped on the
+device -- every row to its best centroid, the mean of every group -- into class prototypes and spherical k-means
+(tfimm_hip_cluster_assign / tfimm_hip_segment_mean, csrc/cluster.hip)."""
 import ctypes as C
 from collections import namedtuple
 
@@ -15,6 +17,14 @@ Matches = namedtuple("Matches", ["indices", "scores"])
 #: what ``Gallery.vote`` / ``Gallery.classify`` return: ``Tensor`` on the device -- int32 classes, float32 values and int32
 #: counts, each (B, top), by value descending, equal values by ascending class, empty slots (-1, 0, 0); float32 total (B,)
 Votes = namedtuple("Votes", ["classes", "values", "counts", "total"])
+
+#: what ``Gallery.assign`` returns: two ``Tensor`` (len,) on the device -- the int32 row of the best centroid of every gallery
+#: row (of equal scores the lowest) and its float32 score
+Assigned = namedtuple("Assigned", ["clusters", "scores"])
+
+#: what ``Gallery.kmeans`` returns: ``centroids`` a labelled ``Gallery`` (label j on row j); ``assignment`` int32 (len,),
+#: ``scores`` float32 (len,), ``counts`` int32 (n_clusters,) of the rows against those centroids; ``moved`` int32 (iters,)
+Clusters = namedtuple("Clusters", ["centroids", "assignment", "scores", "counts", "moved"])
 
 _REDUCE = ("sum", "max")          # TFIMM_KNN_SUM, TFIMM_KNN_MAX
 
@@ -50,7 +60,11 @@ class Gallery:
     label per row lives next to the rows on the device (several rows per person, hundreds per class), every later ``add``
     needs labels, and one more launch behind the search turns the matches into classes: ``vote`` / ``classify`` -- a weighted
     vote, or the best row per identity -- and ``evaluate``, which scores a labelled batch of queries into a ``tfimm.Meter``:
-    the kNN probe of an embedding, with no host trip per batch."""
+    the kNN probe of an embedding, with no host trip per batch.
+
+    Nobody has to organise the gallery beforehand: ``prototypes`` turns a labelled gallery into one row per class (search
+    ``nb_classes`` rows at ``k = 1`` instead of every row at ``k = 20``), ``kmeans`` groups an unlabelled one into
+    pseudo-identities, ``assign`` gives every row its best centroid, and ``set_labels`` hands the groups to the kNN end."""
 
     def __init__(self, dim: int, capacity: int = 0):
         from ..engine import ffi
@@ -398,3 +412,201 @@ class Gallery:
         Three launches on the current stream (tfimm_hip_knn_score behind the search), no synchronisation."""
         t = self._check_rows(q, "evaluate")
         return self._plan_evaluate("Gallery.evaluate", int(t.shape[0]), labels, k, temperature, meter, nb_classes, exclude)(q)
+
+    # -- the cluster end: rows -> groups (csrc/cluster.hip) ------------------------------------------------------------------
+    def set_labels(self, labels) -> None:
+        """Replace the label of every row: ``labels`` (len,), in the forms ``add`` takes, on either side (host labels below -1
+        are refused, device labels are not looked at).  Makes an unlabelled gallery a labelled one:
+        ``gallery.set_labels(clusters.assignment)`` lets ``vote`` / ``classify`` / ``evaluate`` answer with clusters."""
+        import torch
+        up = _row_labels(labels, self._n, "Gallery.set_labels")
+        if self._n:
+            lab = up()
+            if self._lab is None or self._lab.shape[0] < self._capacity:
+                self._lab = torch.full((self._capacity,), -1, dtype=torch.int32, device=lab.device)
+            self._lab[:self._n].copy_(lab)
+        self._labelled = True
+
+    @classmethod
+    def _of_rows(cls, dim, rows, labels):
+        """a labelled gallery over float32 device rows (n, dim) -- rounded to bf16, nearest even -- and int32 labels (n,)"""
+        import torch
+        g = cls(dim)
+        n = int(rows.shape[0])
+        g._buf = torch.zeros((n, g.pitch), dtype=torch.bfloat16, device=rows.device)
+        g._buf[:, :dim].copy_(rows)
+        g._lab = labels.to(torch.int32).contiguous()
+        g._n = g._capacity = n
+        g._labelled = True
+        return g
+
+    def _check_centroids(self, what, centroids) -> None:
+        from ..engine import ffi
+        if not isinstance(centroids, Gallery):
+            raise ValueError(f"{what}: centroids must be a Gallery, got {type(centroids).__name__}")
+        if centroids.dim != self.dim:
+            raise ValueError(f"{what}: centroids of dim {centroids.dim}, this gallery holds rows of {self.dim}")
+        if not 1 <= len(centroids) <= ffi.CLUSTER_MAX_C:
+            raise ValueError(f"{what}: {len(centroids)} centroids, must be in [1, TFIMM_CLUSTER_MAX_C = {ffi.CLUSTER_MAX_C}] "
+                             f"(an empty Gallery holds none)")
+        if not self._n:
+            raise ValueError(f"{what}: the gallery is empty")
+
+    def _launch_assign(self, cbuf, cpitch: int, nc: int):
+        """tfimm_hip_cluster_assign of every row against the bf16 centroids ``cbuf`` (nc, cpitch) on the current stream ->
+        (int32 (len,), float32 (len,)) torch tensors; no synchronisation"""
+        import torch
+        from ..engine import ffi
+        dev = self._buf.device
+        clusters = torch.empty(self._n, dtype=torch.int32, device=dev)
+        scores = torch.empty(self._n, dtype=torch.float32, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(ffi.lib.tfimm_hip_cluster_assign(self._buf.data_ptr(), self.pitch, self._n, cbuf.data_ptr(), cpitch, nc, self.dim,
+                                                   clusters.data_ptr(), scores.data_ptr(), st), "tfimm_hip_cluster_assign")
+        return clusters, scores
+
+    def assign(self, centroids) -> "Assigned":
+        """``Assigned(clusters, scores)``: for every row the row of ``centroids`` -- a ``Gallery`` of the same ``dim`` -- with
+        the largest inner product (of equal scores the lowest) and that score, two ``Tensor`` (len,), int32 / float32.  One
+        launch (tfimm_hip_cluster_assign) on the current stream, no synchronisation; the (len, centroids) score matrix never
+        exists."""
+        self._check_centroids("Gallery.assign", centroids)
+        a, s = self._launch_assign(centroids._buf, centroids.pitch, len(centroids))
+        return Assigned(Tensor(a), Tensor(s))
+
+    def _segment_means(self, groups, nb: int):
+        """the float32 mean (nb, dim) and the int32 count (nb,) of the rows of every group: ``groups`` int32 (len,) on the
+        device, a row whose group is outside [0, nb) belongs to none.  The CSR form is plumbing -- a stable sort of the groups
+        and ``searchsorted`` by ``torch`` on the device --, the means are tfimm_hip_segment_mean; no synchronisation."""
+        import torch
+        from ..engine import ffi
+        dev = groups.device
+        ordered, order = torch.sort(groups, stable=True)
+        offsets = torch.searchsorted(ordered, torch.arange(nb + 1, dtype=torch.int32, device=dev), out_int32=True).contiguous()
+        rows = order.to(torch.int32).contiguous()
+        need = ffi.lib.tfimm_hip_segment_mean_workspace(self._n, nb, self.dim)
+        if need < 0:
+            ffi.check(int(need), "tfimm_hip_segment_mean_workspace")
+        work = self._work.get("segment_mean")
+        if work is None or work.numel() < need:
+            work = self._work["segment_mean"] = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        mean = torch.empty((nb, self.dim), dtype=torch.float32, device=dev)
+        counts = torch.empty(nb, dtype=torch.int32, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(ffi.lib.tfimm_hip_segment_mean(self._buf.data_ptr(), self.pitch, self._n, self.dim, rows.data_ptr(), self._n,
+                                                 offsets.data_ptr(), nb, mean.data_ptr(), self.dim, counts.data_ptr(),
+                                                 work.data_ptr(), work.numel(), st), "tfimm_hip_segment_mean")
+        return mean, counts
+
+    def _normalize(self, x):
+        """tfimm_hip_l2_normalize of the float32 device rows ``x`` (n, dim), in place"""
+        import torch
+        from ..engine import ffi
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(ffi.lib.tfimm_hip_l2_normalize(x.data_ptr(), self.dim, int(x.shape[0]), self.dim, x.data_ptr(), self.dim, st),
+                  "tfimm_hip_l2_normalize")
+        return x
+
+    def prototypes(self, nb_classes=None, normalize: bool = True) -> "Gallery":
+        """One row per class of a labelled gallery: a new labelled ``Gallery`` of ``nb_classes`` rows, row ``c`` the mean of
+        the rows labelled ``c`` (tfimm_hip_segment_mean), L2-normalised if asked (tfimm_hip_l2_normalize), rounded to bf16 and
+        labelled ``c``.  A class without rows gets a zero row labelled -1, so it never votes; labels that are -1 or
+        ``>= nb_classes`` belong to no class.  ``nb_classes=None`` reads the largest label from the device (the one
+        synchronisation); given ``nb_classes`` there is none.  ``prototypes().classify(q, k=1)`` and ``.search(q, 1)`` are the
+        nearest-class-mean classifier: a gallery of ``nb_classes`` rows at ``k = 1``, where the search is at its best."""
+        import torch
+        what = "Gallery.prototypes"
+        self._need_labels(what)
+        if nb_classes is not None and (not _is_int(nb_classes) or not 1 <= nb_classes <= 2 ** 31 - 2):
+            raise ValueError(f"{what}: nb_classes = {nb_classes!r}, must be an integer in [1, 2^31 - 2] or None")
+        if not self._n:
+            raise ValueError(f"{what}: the gallery is empty")
+        lab = self._lab[:self._n]
+        if nb_classes is None:
+            nb_classes = int(lab.max().item()) + 1
+            if nb_classes < 1:
+                raise ValueError(f"{what}: nb_classes: no row of this gallery carries a class (every label is -1)")
+        nb = int(nb_classes)
+        mean, counts = self._segment_means(lab, nb)
+        if normalize:
+            self._normalize(mean)
+        classes = torch.arange(nb, dtype=torch.int32, device=mean.device)
+        return Gallery._of_rows(self.dim, mean, torch.where(counts > 0, classes, torch.full_like(classes, -1)))
+
+    def _plan_kmeans(self, n_clusters, iters, init, seed):
+        """every ``ValueError`` of ``kmeans``; returns the initial centroids as ("rows", int64 indices), ("values", float32
+        (n_clusters, dim) array or tensor) or ("gallery", a ``Gallery`` of n_clusters rows)"""
+        import torch
+        from ..engine import ffi
+        what = "Gallery.kmeans"
+        if not self._n:
+            raise ValueError(f"{what}: the gallery is empty")
+        top = min(self._n, ffi.CLUSTER_MAX_C)
+        if not _is_int(n_clusters) or not 1 <= n_clusters <= top:
+            raise ValueError(f"{what}: n_clusters = {n_clusters!r}, must be an integer in [1, min(len = {self._n}, "
+                             f"TFIMM_CLUSTER_MAX_C = {ffi.CLUSTER_MAX_C})]")
+        if not _is_int(iters) or iters < 0:
+            raise ValueError(f"{what}: iters = {iters!r}, must be an integer that is not negative")
+        k = int(n_clusters)
+        if init is None:
+            return "rows", np.random.default_rng(seed).choice(self._n, k, replace=False).astype(np.int64)
+        if isinstance(init, Gallery):
+            if init.dim != self.dim or len(init) != k:
+                raise ValueError(f"{what}: init: a Gallery of {len(init)} rows of dim {init.dim}, expected {k} rows of {self.dim}")
+            return "gallery", init
+        t = init.torch() if isinstance(init, Tensor) else init
+        if not isinstance(t, torch.Tensor):
+            t = np.asarray(t)
+        kind = str(t.dtype).replace("torch.", "")
+        if kind.startswith(("int", "uint")):
+            a = t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+            if a.shape != (k,):
+                raise ValueError(f"{what}: init: {k} row indices expected, got shape {tuple(a.shape)}")
+            a = a.astype(np.int64)
+            if a.min() < 0 or a.max() >= self._n:
+                raise ValueError(f"{what}: init: row indices must be in [0, len = {self._n}), got values in [{a.min()}, {a.max()}]")
+            if len(np.unique(a)) != k:
+                raise ValueError(f"{what}: init: row indices must be distinct")
+            return "rows", a
+        if kind != "float32":
+            raise ValueError(f"{what}: init: expected row indices (integers) or float32 values, got {t.dtype}")
+        if t.ndim != 2 or tuple(t.shape) != (k, self.dim):
+            raise ValueError(f"{what}: init: expected shape ({k}, {self.dim}), got {tuple(t.shape)}")
+        return "values", t
+
+    def kmeans(self, n_clusters: int, iters: int = 10, init=None, seed: int = 0) -> "Clusters":
+        """Spherical k-means -- Lloyd iterations on the inner product -- over the rows, on the device:
+        ``Clusters(centroids, assignment, scores, counts, moved)``.  Initial centroids: ``init=None`` takes the rows
+        ``np.random.default_rng(seed).choice(len, n_clusters, replace=False)``; ``init`` may be an integer array of
+        ``n_clusters`` distinct row indices, or float32 (n_clusters, dim) values as an array, a ``Tensor`` or a ``Gallery``;
+        they are L2-normalised and rounded to bf16 like all later ones.  An iteration is assign (tfimm_hip_cluster_assign),
+        the CSR form of the groups (``torch``), their means (tfimm_hip_segment_mean), tfimm_hip_l2_normalize, bf16; an empty
+        cluster keeps its previous centroid.  After ``iters`` updates one more assign runs, so that ``assignment`` / ``scores``
+        / ``counts`` (int32, float32, int32 ``Tensor``) belong to the returned ``centroids`` -- a labelled ``Gallery`` with
+        label ``j`` on row ``j`` -- : ``iters + 1`` assign launches, ``iters=0`` only assigns.  ``moved``: int32 ``Tensor``
+        (iters,), the rows whose assignment changed between consecutive assign passes.  Nothing synchronises with the host:
+        callers read ``moved`` if they want a stopping rule."""
+        import torch
+        how, start = self._plan_kmeans(n_clusters, iters, init, seed)
+        k, dev = int(n_clusters), self._buf.device
+        if how == "rows":
+            x = self._buf[torch.from_numpy(start).to(dev), :self.dim].float()
+        elif how == "gallery":
+            x = start._buf[:k, :self.dim].to(dev).float()
+        else:
+            x = self._upload_rows(start).to(dev).float()
+        cen = torch.zeros((k, self.pitch), dtype=torch.bfloat16, device=dev)
+        cen[:, :self.dim].copy_(self._normalize(x.contiguous().clone()))
+        moved = torch.zeros(int(iters), dtype=torch.int32, device=dev)
+        a, s = self._launch_assign(cen, self.pitch, k)
+        for it in range(int(iters)):
+            mean, counts = self._segment_means(a, k)
+            new = self._normalize(mean).to(torch.bfloat16)
+            cen[:, :self.dim] = torch.where((counts > 0)[:, None], new, cen[:, :self.dim])
+            a2, s = self._launch_assign(cen, self.pitch, k)
+            moved[it] = (a2 != a).sum()
+            a = a2
+        counts = torch.zeros(k, dtype=torch.int32, device=dev).scatter_add_(0, a.long(), torch.ones_like(a))
+        centroids = Gallery._of_rows(self.dim, cen[:, :self.dim].float(), torch.arange(k, dtype=torch.int32, device=dev))
+        return Clusters(centroids, Tensor(a), Tensor(s), Tensor(counts), Tensor(moved))
+
