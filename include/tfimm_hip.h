@@ -1085,6 +1085,34 @@ TFIMM_API int64_t tfimm_hip_embed_search_workspace(int B, int N, int E, int k, i
 TFIMM_API int tfimm_hip_embed_search(const float* q, int64_t ld_q, int B, const void* g, int64_t ld_g, int N, int E, int k, int chunk,
                                      float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* tfimm_hip_embed_search_wide (csrc/embed_wide.hip): tfimm_hip_embed_search for up to
+ * TFIMM_EMBED_WIDE_MAX_K neighbours per query -- the same arguments, the same rule (tests/embed_ref.py), the same order, and
+ * the same bits: the scores come from the same loop (csrc/embed_score.h) and the selection is by the same total order, so
+ * wherever both entry points accept a call their scores and indices are bit-equal.
+ * Two launches on `stream`.  Pass 1 scores `chunk` gallery rows per workgroup against 32 queries; every query owns an unsorted
+ * buffer of cap (key, row) pairs in LDS with a threshold, a score that beats the threshold takes a slot by an integer LDS
+ * atomic, and the workgroup prunes every buffer to its k best whenever one could overflow in the next 128 rows; k pairs per
+ * (query, chunk) go to `workspace`, unsorted.  Pass 2 streams them through one buffer per query and orders the k survivors by
+ * rank.  What a prune keeps is the k best of the buffer's content under a total order, whatever the order of arrival: the
+ * result does not depend on chunk, on B, on which queries share a call or on timing; bit-reproducible, no float atomics, no
+ * scratch memory, no allocation, capturable.  The B x N score matrix never exists.
+ * chunk == 0: the library chooses (never fewer than 4 k rows, in multiples of 128); otherwise a positive multiple of 32.  There
+ * is no limit on ceil(N / chunk).
+ * Limits: 1 <= k <= min(N, TFIMM_EMBED_WIDE_MAX_K); E, N, B, ld_q, ld_g and alignment as for tfimm_hip_embed_search; and the
+ * buffers must fit LDS next to the query tile: 32 (2 E + 16) + 32 * 8 * cap <= 160 KiB with cap >= k + 128 (the library takes
+ * cap = k + 256 where that fits without costing a workgroup per CU) -- every k <= 256 up to E = 768, k <= 254 at E = 1024, none at E = 2048.
+ * tfimm_hip_embed_search_wide_max_k(E) returns the largest k this E allows, 0 or less where there is none (and 0 for an E
+ * outside the domain); a (E, k) pair that does not fit is TFIMM_EINVAL with a message naming both.
+ * workspace_bytes >= tfimm_hip_embed_search_wide_workspace(B, N, E, k, chunk) (TFIMM_EINVAL, negative, for arguments the
+ * search would refuse).  Everything else is TFIMM_EINVAL before any launch, with a message naming the argument.  B == 0
+ * returns 0 and launches nothing. */
+#define TFIMM_EMBED_WIDE_MAX_K 256
+TFIMM_API int tfimm_hip_embed_search_wide_max_k(int E);
+TFIMM_API int64_t tfimm_hip_embed_search_wide_workspace(int B, int N, int E, int k, int chunk);
+TFIMM_API int tfimm_hip_embed_search_wide(const float* q, int64_t ld_q, int B, const void* g, int64_t ld_g, int N, int E, int k,
+                                          int chunk, float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes,
+                                          void* stream);
+
 /* =======================================================================================
  * KNN END (csrc/knn.hip; the CPU restatement of the rule is tests/knn_ref.py): the matches of a gallery
  * search turned into classes through a label per gallery row, in one launch behind tfimm_hip_embed_search.

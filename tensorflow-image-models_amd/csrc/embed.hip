@@ -14,7 +14,8 @@
 //   comes straight from global memory: lane (r, h) holds A[row r][k = 8h .. 8h+7], 16 contiguous bytes of gallery row r.  k is
 //   permuted identically on both operands so that within 64 columns lane (r, h) owns columns 32h .. 32h+31: it reads 64
 //   contiguous bytes of its row per four MFMA steps (the < 64 columns behind the last full group use the plain map).  The
-//   32 x 32 float32 tile has the query on the lane (column = lane & 31) and 16 gallery rows in the registers.
+//   32 x 32 float32 tile has the query on the lane (column = lane & 31) and 16 gallery rows in the registers.  (The query
+//   tile and this loop are embed_score.h, shared with tfimm_hip_embed_search_wide, embed_wide.hip.)
 //   Every (wave, query) owns a list of k (key, row) pairs in LDS, ordered by (key descending, row ascending) -- the keys of
 //   topk_select.h, 0 = empty.  A lane compares its 16 scores with the list's last entry and inserts the few that beat it; the
 //   two lanes of a query (h = 0, 1) take turns, so a list has one writer at a time.  The list is the k best of what the wave
@@ -28,11 +29,13 @@
 // No atomics, no scratch memory, every reduction in a fixed order; a score is a function of its query and its gallery row
 // alone (the k loop does not depend on B, chunk or the tile's other queries), and the selection is by a total order: results
 // are bit-reproducible and independent of B and chunk.
+#include "embed_score.h"
 #include "topk_select.h"
 
 namespace {
 
 using namespace topk_sel;
+using namespace embed_score;
 
 // ------------------------------------------------------------------------------------------------------------------------
 // l2_normalize
@@ -59,9 +62,6 @@ __global__ void __launch_bounds__(64 * kNormRows) l2_normalize_kernel(const floa
 // ------------------------------------------------------------------------------------------------------------------------
 // embed_search
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int kQTile = 32;                      // queries per workgroup: the N dimension of the MFMA
-constexpr int kRowTile = 32;                    // gallery rows per MFMA tile
-constexpr int kLdsBudget = 160 * 1024;          // gfx950: LDS per workgroup
 static_assert(TFIMM_EMBED_MAX_B == 65535 * kQTile, "query tiles are grid.y");
 constexpr int kPass2MaxCand = 16384;            // candidate keys pass 2 holds in LDS (64 KiB)
 
@@ -73,12 +73,6 @@ struct SearchArgs {
   int64_t ld_q, ld_g;
   int B, N, E, k, chunk, chunks, list_waves;
 };
-
-// float32 -> bf16 bits, round to nearest even; a NaN stays a (quiet) NaN
-__device__ __forceinline__ uint32_t bf16_rne(uint32_t b) {
-  if ((b & 0x7fffffffu) > 0x7f800000u) return (b >> 16) | 0x40u;
-  return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
-}
 
 __device__ __forceinline__ void list_insert(uint32_t* lk, int* li, int k, uint32_t key, int row) {
   int j = k - 1;
@@ -98,22 +92,13 @@ __global__ void __launch_bounds__(kThreads) embed_search_pass1(SearchArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int E = a.E, k = a.k;
-  const int pitch = 2 * E + 16;                                   // bytes per query row in LDS
+  const int pitch = query_pitch(E);                               // bytes per query row in LDS
   uint32_t* list_key = reinterpret_cast<uint32_t*>(smem + (size_t)kQTile * pitch);   // [list_waves][32][k]
   int* list_idx = reinterpret_cast<int*>(list_key + a.list_waves * kQTile * k);
   const int q0 = blockIdx.y * kQTile;
 
   // ---- the query tile -> bf16 in LDS (queries past B: zeros), the lists -> empty
-  for (int i = tid; i < kQTile * (E / 2); i += kThreads) {
-    const int qi = i / (E / 2), c = (i - qi * (E / 2)) * 2;
-    uint32_t lo = 0, hi = 0;
-    if (q0 + qi < a.B) {
-      const float* src = a.q + (int64_t)(q0 + qi) * a.ld_q + c;
-      lo = bf16_rne(__float_as_uint(src[0]));
-      hi = bf16_rne(__float_as_uint(src[1]));
-    }
-    *reinterpret_cast<uint32_t*>(smem + (size_t)qi * pitch + 2 * c) = lo | (hi << 16);
-  }
+  load_query_tile(smem, a.q, a.ld_q, q0, a.B, E, tid, kThreads);
   for (int i = tid; i < a.list_waves * kQTile * k; i += kThreads) {
     list_key[i] = kRetired;
     list_idx[i] = INT_MAX;
@@ -134,23 +119,7 @@ __global__ void __launch_bounds__(kThreads) embed_search_pass1(SearchArgs a) {
       // a row past the gallery reads the last row instead (its scores are never looked at)
       const int64_t grow = min(base + r, (int64_t)a.N - 1);
       const uint16_t* ga = a.g + grow * a.ld_g;
-      f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int gi = 0; gi < groups; ++gi) {
-        const uint4* ap = reinterpret_cast<const uint4*>(ga + gi * 64 + h * 32);
-        const uint4* bp = reinterpret_cast<const uint4*>(qrow + 2 * (gi * 64 + h * 32));
-        const uint4 a0 = ap[0], a1 = ap[1], a2 = ap[2], a3 = ap[3];
-        const uint4 b0 = bp[0], b1 = bp[1], b2 = bp[2], b3 = bp[3];
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a0), __builtin_bit_cast(bf16x8, b0), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a1), __builtin_bit_cast(bf16x8, b1), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a2), __builtin_bit_cast(bf16x8, b2), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a3), __builtin_bit_cast(bf16x8, b3), acc, 0, 0, 0);
-      }
-      for (int t = 0; t < tail; ++t) {
-        const int c = groups * 64 + t * 16 + h * 8;
-        const uint4 av = *reinterpret_cast<const uint4*>(ga + c);
-        const uint4 bv = *reinterpret_cast<const uint4*>(qrow + 2 * c);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
-      }
+      const f32x16 acc = score_tile(ga, qrow, h, groups, tail);
       // ---- lane (r, h): query q0 + r, gallery rows base + (i & 3) + 8 (i >> 2) + 4 h.  h = 0 inserts, then h = 1.
 #pragma unroll
       for (int phase = 0; phase < 2; ++phase) {
@@ -242,7 +211,7 @@ int choose_chunk(int B, int N, int k) {
   return (int)chunk;
 }
 
-int pass1_lds_bytes(int E, int k, int list_waves) { return kQTile * (2 * E + 16) + list_waves * kQTile * k * 8; }
+int pass1_lds_bytes(int E, int k, int list_waves) { return kQTile * query_pitch(E) + list_waves * kQTile * k * 8; }
 
 // validates (N, k, chunk) and resolves chunk = 0; returns an error text or nullptr
 const char* resolve_chunk(int B, int N, int E, int k, int* chunk, int64_t* chunks) {

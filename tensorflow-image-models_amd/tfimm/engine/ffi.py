@@ -272,6 +272,10 @@ SYMBOLS = {
     "tfimm_hip_l2_normalize": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp]),
     "tfimm_hip_embed_search_workspace": (_i64, [_i, _i, _i, _i, _i]),
     "tfimm_hip_embed_search": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    # the search for up to 256 neighbours (csrc/embed_wide.hip): E | then as tfimm_hip_embed_search
+    "tfimm_hip_embed_search_wide_max_k": (_i, [_i]),
+    "tfimm_hip_embed_search_wide_workspace": (_i64, [_i, _i, _i, _i, _i]),
+    "tfimm_hip_embed_search_wide": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     # the kNN end (csrc/knn.hip): indices, scores, ld, B, k, glabels, N, exclude, inv_temperature, then
     # reduce, top, classes, values, counts, total | nb_classes, labels, loss, rank, pred, prob, state, per_class, confusion
     "tfimm_hip_knn_vote": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -416,6 +420,7 @@ DISTILL_MAX_E = 4096              # tfimm_hip_distill_grad: columns of an embedd
 # include/tfimm_hip.h: the domain of tfimm_hip_embed_search (E a multiple of 16; the gallery row pitch a multiple of 8 elements)
 EMBED_MIN_E, EMBED_MAX_E, EMBED_MAX_K = 16, 2048, 64
 EMBED_MAX_B = 65535 * 32          # queries per call: tiles of 32 are one grid dimension
+EMBED_WIDE_MAX_K = 256            # tfimm_hip_embed_search_wide; what a width E allows: tfimm_hip_embed_search_wide_max_k(E)
 # include/tfimm_hip.h: the domain of tfimm_hip_knn_vote / tfimm_hip_knn_score (one lane per candidate and per slot of the list)
 KNN_MAX_K, KNN_MAX_TOP, KNN_SUM, KNN_MAX = EMBED_MAX_K, 64, 0, 1
 # include/tfimm_hip.h: centroids per tfimm_hip_cluster_assign; entries per run of tfimm_hip_segment_mean's summation rule

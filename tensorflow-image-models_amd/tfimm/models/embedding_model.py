@@ -161,17 +161,17 @@ class EmbeddingModel(Model):
     def evaluate(self, x, labels, meter=None, training: bool = False):
         raise ValueError(f"{self.name}: evaluate needs a classifier, an embedding model has none (search a Gallery instead)")
 
-    def search(self, x, gallery, k: int = 5):
-        """``gallery.search(model(x), k)``: the model's recording, then the two launches of the search, on the same stream;
-        ``Matches(indices, scores)``, each (B, k).  The embeddings never leave the device."""
+    def search(self, x, gallery, k: int = 5, method: str = "auto"):
+        """``gallery.search_with(model(x), k, method=method)``: the model's recording, then the two launches of the search, on the
+        same stream; ``Matches(indices, scores)``, each (B, k), ``k`` up to 256.  The embeddings never leave the device."""
         if gallery.dim != self.embed_dim:
             raise ValueError(f"{self.name}: embeddings have {self.embed_dim} columns, the gallery holds rows of {gallery.dim}")
-        gallery._check_k(k)
+        gallery._route(k, method)
         emb = self(x)
         if len(emb.shape) != 2:
             raise ValueError(f"{self.name}: embeddings are a map {emb.shape} (the backbone's forward_features is one): a gallery "
                              f"holds one row per image, pool the map first")
-        return gallery.search(emb, k)
+        return gallery.search_with(emb, k, method=method)
 
     def _embeddings_for(self, x, gallery):
         emb = self(x)

@@ -1,5 +1,6 @@
 """``Gallery``: embeddings to search, resident on the device as bf16, and the fused search over them
-(tfimm_hip_embed_search, csrc/embed.hip); with a label per row, the matches turned into classes and
+(tfimm_hip_embed_search, csrc/embed.hip; for up to 256 neighbours tfimm_hip_embed_search_wide,
+csrc/embed_wide.hip); with a label per row, the matches turned into classes and
 scored on the device (tfimm_hip_knn_vote / tfimm_hip_knn_score, csrc/knn.hip); and the rows grouped on the
 device -- every row to its best centroid, the mean of every group -- into class prototypes and spherical k-means
 (tfimm_hip_cluster_assign / tfimm_hip_segment_mean, csrc/cluster.hip)."""
@@ -27,6 +28,12 @@ Assigned = namedtuple("Assigned", ["clusters", "scores"])
 Clusters = namedtuple("Clusters", ["centroids", "assignment", "scores", "counts", "moved"])
 
 _REDUCE = ("sum", "max")          # TFIMM_KNN_SUM, TFIMM_KNN_MAX
+_METHODS = ("auto", "list", "buffer")
+
+#: the smallest ``k <= 64`` from which ``Gallery.search`` (``search_with(method="auto")``) takes the buffer path
+#: (tfimm_hip_embed_search_wide): the smallest probed k from which its median lay below the list path's minimum at every shape of that k in
+#: profiles/search_wide_probe.txt (k = 5 loses, k = 20 and k = 64 win); 65 would keep the list path throughout
+SEARCH_BUFFER_FROM_K = 20
 
 
 def _is_int(v) -> bool:
@@ -79,7 +86,7 @@ class Gallery:
         self._capacity = int(capacity)
         self._n = 0
         self._buf = None                              # torch.bfloat16 (capacity, pitch), allocated on the first add
-        self._work = {}                               # (B, k) -> workspace of the search (uint8)
+        self._work = {}                               # (B, k, path) -> workspace of the search (uint8)
         self._labelled = False
         self._lab = None                              # torch.int32 (capacity,), a labelled gallery's label per row
 
@@ -203,21 +210,54 @@ class Gallery:
             return np.zeros((0, self.dim), np.float32)
         return self._buf[:self._n, :self.dim].float().cpu().numpy()
 
-    def _check_k(self, k) -> None:
+    def _route(self, k, method="auto") -> str:
+        """every ``ValueError`` of ``search`` about ``k`` and ``method``; returns the path the search takes: ``"list"``
+        (tfimm_hip_embed_search) or ``"buffer"`` (tfimm_hip_embed_search_wide).  No device work."""
         from ..engine import ffi
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
             raise ValueError(f"Gallery.search: k must be an integer, got {k!r}")
-        if k < 1 or k > self._n or k > ffi.EMBED_MAX_K:
-            raise ValueError(f"Gallery.search: k = {k}, must be in [1, min(len = {self._n}, TFIMM_EMBED_MAX_K = {ffi.EMBED_MAX_K})]")
+        if method not in _METHODS:
+            raise ValueError(f"Gallery.search: method = {method!r}, must be one of {', '.join(map(repr, _METHODS))}")
+        if k < 1 or k > self._n or k > ffi.EMBED_WIDE_MAX_K:
+            raise ValueError(f"Gallery.search: k = {k}, must be in [1, min(len = {self._n}, TFIMM_EMBED_WIDE_MAX_K = "
+                             f"{ffi.EMBED_WIDE_MAX_K})]")
+        if method == "list":
+            if k > ffi.EMBED_MAX_K:
+                raise ValueError(f"Gallery.search: k = {k} with method='list', whose limit is TFIMM_EMBED_MAX_K = {ffi.EMBED_MAX_K} "
+                                 f"(method='buffer' or 'auto' go up to {ffi.EMBED_WIDE_MAX_K})")
+            return "list"
+        wide = int(ffi.lib.tfimm_hip_embed_search_wide_max_k(self.dim))     # what the LDS next to a query tile of this width holds
+        if method == "buffer" and k > wide:
+            raise ValueError(f"Gallery.search: k = {k} with method='buffer': rows of dim {self.dim} allow "
+                             f"{'k <= ' + str(wide) if wide > 0 else 'no k'} on this path (tfimm_hip_embed_search_wide_max_k)")
+        if k > ffi.EMBED_MAX_K and k > wide:
+            raise ValueError(f"Gallery.search: k = {k}: rows of dim {self.dim} allow k <= {max(wide, ffi.EMBED_MAX_K)} "
+                             f"(tfimm_hip_embed_search_wide_max_k({self.dim}) = {wide}, TFIMM_EMBED_MAX_K = {ffi.EMBED_MAX_K})")
+        if method == "buffer" or k > ffi.EMBED_MAX_K or (SEARCH_BUFFER_FROM_K <= k <= wide):
+            return "buffer"
+        return "list"
 
     def search(self, q, k: int = 5, chunk: int = 0) -> Matches:
         """``Matches(indices, scores)`` for float32 queries ``q`` (B, dim), a ``Tensor`` or an array: per query the ``k``
         gallery rows with the largest ``sum_e bf16(q)[e] * row[e]``, score descending, equal scores by ascending row.  Two
         launches on the current stream, behind whatever produced ``q`` there.  ``chunk``: gallery rows per workgroup of the
-        first pass, 0 = the library chooses; the result does not depend on it."""
+        first pass, 0 = the library chooses; the result does not depend on it.
+
+        ``k`` goes up to 256 (``TFIMM_EMBED_WIDE_MAX_K``; at ``dim > 768`` up to what
+        ``tfimm_hip_embed_search_wide_max_k(dim)`` allows, and never less than 64).  This is ``search_with(q, k, chunk,
+        method="auto")``: the route changes time only.  ``vote`` takes ``Matches`` of at most 64 columns: ``vote``,
+        ``classify`` and ``evaluate`` keep ``k <= 64``."""
+        return self.search_with(q, k, chunk, "auto")
+
+    def search_with(self, q, k: int = 5, chunk: int = 0, method: str = "auto") -> Matches:
+        """``search`` by a chosen selection.  ``method``: ``"list"`` keeps the ``k`` best in sorted lists
+        (tfimm_hip_embed_search, ``k <= 64``), ``"buffer"`` in unsorted buffers that are pruned (tfimm_hip_embed_search_wide,
+        ``k <= 256``); both give the same bits, so ``"auto"`` -- the buffer path for ``k > 64`` and from
+        ``SEARCH_BUFFER_FROM_K`` upwards, the list path below and wherever the width allows no buffers -- changes time only.
+        ``search`` keeps the signature it had; the choice lives here."""
         import torch
         from ..engine import ffi
-        self._check_k(k)
+        path = self._route(k, method)
         t = self._rows(q, "search").contiguous()
         B, k = int(t.shape[0]), int(k)
         if B > ffi.EMBED_MAX_B:
@@ -226,16 +266,16 @@ class Gallery:
         indices = torch.empty((B, k), dtype=torch.int32, device=t.device)
         if B == 0:
             return Matches(Tensor(indices), Tensor(scores))
-        need = ffi.lib.tfimm_hip_embed_search_workspace(B, self._n, self.dim, k, chunk)
+        name = "tfimm_hip_embed_search" if path == "list" else "tfimm_hip_embed_search_wide"
+        need = getattr(ffi.lib, name + "_workspace")(B, self._n, self.dim, k, chunk)
         if need < 0:
-            ffi.check(int(need), "tfimm_hip_embed_search_workspace")
-        work = self._work.get((B, k))
+            ffi.check(int(need), name + "_workspace")
+        work = self._work.get((B, k, path))
         if work is None or work.numel() < need:
-            work = self._work[(B, k)] = torch.empty(int(need), dtype=torch.uint8, device=t.device)
+            work = self._work[(B, k, path)] = torch.empty(int(need), dtype=torch.uint8, device=t.device)
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        ffi.check(ffi.lib.tfimm_hip_embed_search(t.data_ptr(), self.dim, B, self._buf.data_ptr(), self.pitch, self._n, self.dim, k,
-                                                 int(chunk), scores.data_ptr(), indices.data_ptr(), work.data_ptr(),
-                                                 work.numel(), st), "tfimm_hip_embed_search")
+        ffi.check(getattr(ffi.lib, name)(t.data_ptr(), self.dim, B, self._buf.data_ptr(), self.pitch, self._n, self.dim, k,
+                                         int(chunk), scores.data_ptr(), indices.data_ptr(), work.data_ptr(), work.numel(), st), name)
         return Matches(Tensor(indices), Tensor(scores))
 
     # -- the kNN end: matches -> classes (csrc/knn.hip) ----------------------------------------------------------------------
@@ -326,7 +366,8 @@ class Gallery:
         identity that is missing has its best row below the k-th score).  ``counts``: the matches of each class.  Order: value
         descending, equal values by ascending class; slots beyond the distinct classes hold (-1, 0, 0).  Rows labelled -1
         never vote, nor does ``exclude[b]`` -- an int vector (B,), the gallery row query ``b`` must not meet (itself, in a
-        leave-one-out evaluation; -1: none).  One launch (tfimm_hip_knn_vote) on the current stream, no synchronisation."""
+        leave-one-out evaluation; -1: none).  One launch (tfimm_hip_knn_vote) on the current stream, no synchronisation.
+        ``Matches`` of more than 64 columns (``TFIMM_KNN_MAX_K``) -- ``search`` returns up to 256 -- are refused."""
         what = "Gallery.vote"
         self._need_labels(what)
         inv_t, red = self._vote_args(what, temperature, top, reduce)
