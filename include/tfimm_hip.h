@@ -1113,6 +1113,47 @@ TFIMM_API int tfimm_hip_embed_search_wide(const float* q, int64_t ld_q, int B, c
                                           int chunk, float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes,
                                           void* stream);
 
+/* tfimm_hip_embed_quantize_rows / tfimm_hip_embed_search_coarse (csrc/embed_coarse.hip; the CPU restatement of
+ * the rule is tests/coarse_ref.py): a coarse-to-fine search.  The gallery is scanned as one OCP e4m3fn byte per element, the
+ * scan keeps `candidates` rows per query, and only those are scored in bf16 by the loop of tfimm_hip_embed_search: a returned
+ * score has the bits the exact searches give for that row, and where the candidates contain the true top k the whole result
+ * is bit-equal to theirs.  The order of rows is untouched and nothing depends on a clustering.
+ *
+ * tfimm_hip_embed_quantize_rows: for each of N bf16 rows g [N][ld_g] of E values, a = max |g_e|, exps[n] = 0 if a == 0 and
+ * otherwise ceil(log2(a / 448)) clamped to [-126, 126], codes[n][e] = e4m3fn(g[n][e] * 2^-exps[n]), round to nearest even.
+ * The scale is a power of two, so scaling is exact, and nothing saturates.  codes uint8 [N][ld_c], ld_c >= E bytes and a
+ * multiple of 16; exps int8 [N].  One wave per row, every row read once, nothing written behind E code bytes of a row.  A
+ * non-finite entry becomes the NaN code 0x7f with its sign.  g and codes 16-byte aligned; E and ld_g as for
+ * tfimm_hip_embed_search; 0 <= N < 2^31, N == 0 launches nothing.  Rows may be quantised in any number of calls.
+ *
+ * tfimm_hip_embed_search_coarse: q, g, scores, indices as for tfimm_hip_embed_search; codes / exps the quantised rows of g.
+ *   coarse key (b, n) = (float32 MFMA sum over e of code(q16[b])[e] * codes[n][e], from a zero accumulator) * 2^exps[n], the
+ *   query rounded to bf16 and quantised by the rule above (its own exponent, a positive constant per query, is not applied);
+ *   the `candidates` best rows per query by key descending, equal keys by ascending row; their exact scores; the k best of
+ *   those by score descending, equal scores by ascending row.
+ * Three launches on `stream`: pass 1 is pass 1 of tfimm_hip_embed_search_wide over the codes with k = candidates (the query
+ * tile as fp8 in LDS, v_mfma_f32_32x32x16_fp8_fp8), pass 2 merges the chunks, pass 3 scores the candidates of a query with
+ * the bf16 loop and ranks the k best by counting.  The result does not depend on B, on chunk, on which queries share a call
+ * or on timing; no float atomics, no scratch memory, no allocation, capturable.
+ * Gallery rows are assumed finite.  A row with a non-finite entry has a NaN key, which orders above every number, as a NaN
+ * score does in the exact searches: it is a candidate of every query (while there are no more than `candidates` such rows) and
+ * is then scored exactly; nothing faults or hangs.
+ * Limits: E, B, N, ld_q, ld_g, chunk and alignment as for tfimm_hip_embed_search_wide; ld_c >= E and a multiple of 16 bytes,
+ * codes 16-byte and exps 4-byte aligned; 1 <= k <= candidates <= min(N, tfimm_hip_embed_search_coarse_max_candidates(E)), which
+ * is what LDS holds next to the fp8 query tile -- 32 (E + 16) + 32 * 8 * cap <= 160 KiB with cap >= candidates + 128, at most
+ * TFIMM_EMBED_COARSE_MAX_CANDIDATES: 256 up to E = 2032, 254 at E = 2048 (0 for an E outside the domain).
+ * workspace_bytes >= tfimm_hip_embed_search_coarse_workspace(B, N, E, k, candidates, chunk) (TFIMM_EINVAL, negative, for
+ * arguments the search would refuse).  Everything else is TFIMM_EINVAL before any launch, with a message naming the
+ * argument.  B == 0 returns 0 and launches nothing. */
+#define TFIMM_EMBED_COARSE_MAX_CANDIDATES 256
+TFIMM_API int tfimm_hip_embed_quantize_rows(const void* g, int64_t ld_g, int N, int E, void* codes, int64_t ld_c, int8_t* exps,
+                                            void* stream);
+TFIMM_API int tfimm_hip_embed_search_coarse_max_candidates(int E);
+TFIMM_API int64_t tfimm_hip_embed_search_coarse_workspace(int B, int N, int E, int k, int candidates, int chunk);
+TFIMM_API int tfimm_hip_embed_search_coarse(const float* q, int64_t ld_q, int B, const void* g, int64_t ld_g, const void* codes,
+                                            int64_t ld_c, const int8_t* exps, int N, int E, int k, int candidates, int chunk,
+                                            float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =======================================================================================
  * KNN END (csrc/knn.hip; the CPU restatement of the rule is tests/knn_ref.py): the matches of a gallery
  * search turned into classes through a label per gallery row, in one launch behind tfimm_hip_embed_search.

@@ -173,6 +173,15 @@ class EmbeddingModel(Model):
                              f"holds one row per image, pool the map first")
         return gallery.search_with(emb, k, method=method)
 
+    def search_coarse(self, x, gallery, k: int = 5, candidates=None):
+        """``gallery.search_coarse(model(x), k, candidates)``: the model's recording, then the three launches of the
+        coarse-to-fine search (fp8 scan, merge, exact bf16 rerank), on the same stream; ``Matches(indices, scores)``, each
+        (B, k).  The gallery needs its coarse copy (``gallery.build_coarse()``)."""
+        if gallery.dim != self.embed_dim:
+            raise ValueError(f"{self.name}: embeddings have {self.embed_dim} columns, the gallery holds rows of {gallery.dim}")
+        gallery._coarse_args(k, candidates)
+        return gallery.search_coarse(self._embeddings_for(x, gallery), k, candidates)
+
     def _embeddings_for(self, x, gallery):
         emb = self(x)
         if len(emb.shape) != 2:

@@ -1,6 +1,7 @@
 """``Gallery``: embeddings to search, resident on the device as bf16, and the fused search over them
 (tfimm_hip_embed_search, csrc/embed.hip; for up to 256 neighbours tfimm_hip_embed_search_wide,
-csrc/embed_wide.hip); with a label per row, the matches turned into classes and
+csrc/embed_wide.hip; coarse to fine over an fp8 copy of the rows tfimm_hip_embed_search_coarse,
+csrc/embed_coarse.hip); with a label per row, the matches turned into classes and
 scored on the device (tfimm_hip_knn_vote / tfimm_hip_knn_score, csrc/knn.hip); and the rows grouped on the
 device -- every row to its best centroid, the mean of every group -- into class prototypes and spherical k-means
 (tfimm_hip_cluster_assign / tfimm_hip_segment_mean, csrc/cluster.hip)."""
@@ -89,6 +90,10 @@ class Gallery:
         self._work = {}                               # (B, k, path) -> workspace of the search (uint8)
         self._labelled = False
         self._lab = None                              # torch.int32 (capacity,), a labelled gallery's label per row
+        self._coarse = False                          # build_coarse: an fp8 copy of the rows for search_coarse
+        self._codes = None                            # torch.uint8 (capacity, dim): e4m3fn codes, row pitch dim (a multiple of 16)
+        self._exps = None                             # torch.int8 (capacity,): the power of two of every row's scale
+        self._work_coarse = {}                        # (B, k, candidates) -> workspace of search_coarse (uint8)
 
     def __len__(self) -> int:
         return self._n
@@ -165,6 +170,9 @@ class Gallery:
                 buf[:self._n].copy_(self._buf[:self._n])
             self._buf, self._capacity = buf, cap
         self._buf[self._n:self._n + n, :self.dim].copy_(t)           # float32 -> bf16: nearest even
+        if self._coarse:                                             # the fp8 copy grows with the rows and takes the new ones
+            self._grow_coarse()
+            self._quantize(self._n, n)
         if up_labels is not None:
             self._labelled = True
             if self._lab is None or self._lab.shape[0] < self._capacity:     # grows with the rows
@@ -276,6 +284,102 @@ class Gallery:
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         ffi.check(getattr(ffi.lib, name)(t.data_ptr(), self.dim, B, self._buf.data_ptr(), self.pitch, self._n, self.dim, k,
                                          int(chunk), scores.data_ptr(), indices.data_ptr(), work.data_ptr(), work.numel(), st), name)
+        return Matches(Tensor(indices), Tensor(scores))
+
+    # -- the coarse-to-fine search: fp8 scan, exact bf16 rerank (csrc/embed_coarse.hip) ---------------------------
+    @property
+    def coarse(self) -> bool:
+        """whether the rows have an fp8 copy (``build_coarse``), which ``search_coarse`` scans"""
+        return self._coarse
+
+    def _grow_coarse(self) -> None:
+        """codes and exponents for ``capacity`` rows; those of the first ``len`` rows are kept"""
+        import torch
+        if self._buf is None or (self._codes is not None and self._codes.shape[0] >= self._capacity):
+            return
+        codes = torch.zeros((self._capacity, self.dim), dtype=torch.uint8, device=self._buf.device)
+        exps = torch.zeros(self._capacity, dtype=torch.int8, device=self._buf.device)
+        if self._codes is not None and self._n:
+            codes[:self._n].copy_(self._codes[:self._n])
+            exps[:self._n].copy_(self._exps[:self._n])
+        self._codes, self._exps = codes, exps
+
+    def _quantize(self, first: int, n: int) -> None:
+        """tfimm_hip_embed_quantize_rows of rows ``first .. first + n`` on the current stream; no synchronisation"""
+        import torch
+        from ..engine import ffi
+        if not n:
+            return
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(ffi.lib.tfimm_hip_embed_quantize_rows(self._buf.data_ptr() + 2 * first * self.pitch, self.pitch, n, self.dim,
+                                                        self._codes.data_ptr() + first * self.dim, self.dim,
+                                                        self._exps.data_ptr() + first, st), "tfimm_hip_embed_quantize_rows")
+
+    def build_coarse(self) -> None:
+        """Give the gallery an fp8 copy of its rows for ``search_coarse``: per row one power-of-two scale (int8) and ``dim``
+        OCP e4m3fn codes (tfimm_hip_embed_quantize_rows), ``dim + 1`` bytes next to the ``2 dim`` of the bf16 row.  From then
+        on ``add`` quantises the rows it appends.  Calling it again quantises every row anew.  One launch on the current
+        stream, no synchronisation; ``search`` and everything else are untouched."""
+        self._coarse = True
+        self._codes = self._exps = None
+        self._grow_coarse()
+        if self._buf is not None:
+            self._quantize(0, self._n)
+
+    def _coarse_args(self, k, candidates):
+        """every ``ValueError`` of ``search_coarse`` about the gallery, ``k`` and ``candidates``; returns ``candidates``
+        resolved.  No device work."""
+        from ..engine import ffi
+        what = "Gallery.search_coarse"
+        if not self._coarse:
+            raise ValueError(f"{what}: this gallery has no coarse copy: call build_coarse() first")
+        if not _is_int(k):
+            raise ValueError(f"{what}: k must be an integer, got {k!r}")
+        if candidates is not None and not _is_int(candidates):
+            raise ValueError(f"{what}: candidates must be an integer or None, got {candidates!r}")
+        most = int(ffi.lib.tfimm_hip_embed_search_coarse_max_candidates(self.dim))
+        c = min(max(4 * int(k), 32), most, self._n) if candidates is None else int(candidates)
+        if c > most:
+            raise ValueError(f"{what}: candidates = {c}: rows of dim {self.dim} allow candidates <= {most} "
+                             f"(tfimm_hip_embed_search_coarse_max_candidates)")
+        if c > self._n:
+            raise ValueError(f"{what}: candidates = {c}, must be in [1, len = {self._n}]")
+        if k < 1 or k > c:
+            raise ValueError(f"{what}: k = {k}, must be in [1, candidates = {c}]")
+        return c
+
+    def search_coarse(self, q, k: int = 5, candidates=None, chunk: int = 0) -> Matches:
+        """``Matches(indices, scores)`` as ``search`` gives them, by a coarse-to-fine search: every row is scanned as fp8 codes
+        (``build_coarse``), the ``candidates`` rows with the largest coarse keys per query are scored exactly as ``search``
+        scores them, and the ``k`` best of those are returned, score descending, equal scores by ascending row.  Every
+        returned score has the bits ``search`` gives for that row; where the candidates contain the true top ``k`` -- with
+        ``candidates = 4 k`` on random data always, on tightly clustered data not always -- the whole result
+        is bit-equal.  ``candidates=None`` means ``min(max(4 k, 32), max_candidates(dim), len)``; at most
+        ``tfimm_hip_embed_search_coarse_max_candidates(dim)`` (256, 254 at ``dim = 2048``).  Three launches on the current
+        stream; the result does not depend on ``chunk``.  ``vote`` takes the matches as it takes those of ``search``."""
+        import torch
+        from ..engine import ffi
+        c = self._coarse_args(k, candidates)
+        t = self._rows(q, "search_coarse").contiguous()
+        B, k = int(t.shape[0]), int(k)
+        if B > ffi.EMBED_MAX_B:
+            raise ValueError(f"Gallery.search_coarse: {B} queries, at most TFIMM_EMBED_MAX_B = {ffi.EMBED_MAX_B} per call")
+        scores = torch.empty((B, k), dtype=torch.float32, device=t.device)
+        indices = torch.empty((B, k), dtype=torch.int32, device=t.device)
+        if B == 0:
+            return Matches(Tensor(indices), Tensor(scores))
+        name = "tfimm_hip_embed_search_coarse"
+        need = ffi.lib.tfimm_hip_embed_search_coarse_workspace(B, self._n, self.dim, k, c, chunk)
+        if need < 0:
+            ffi.check(int(need), name + "_workspace")
+        work = self._work_coarse.get((B, k, c))
+        if work is None or work.numel() < need:
+            work = self._work_coarse[(B, k, c)] = torch.empty(int(need), dtype=torch.uint8, device=t.device)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(ffi.lib.tfimm_hip_embed_search_coarse(t.data_ptr(), self.dim, B, self._buf.data_ptr(), self.pitch,
+                                                        self._codes.data_ptr(), self.dim, self._exps.data_ptr(), self._n, self.dim,
+                                                        k, c, int(chunk), scores.data_ptr(), indices.data_ptr(), work.data_ptr(),
+                                                        work.numel(), st), name)
         return Matches(Tensor(indices), Tensor(scores))
 
     # -- the kNN end: matches -> classes (csrc/knn.hip) ----------------------------------------------------------------------
