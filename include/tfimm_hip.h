@@ -702,6 +702,29 @@ typedef struct tfimm_chain_desc {
 TFIMM_API int tfimm_hip_conv_chain(const tfimm_chain_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * tfimm_hip_conv_chain_next: tfimm_hip_conv_chain with the 1x1 convolution that READS its result -- conv1 / bn1 / act1 of
+ * the following bottleneck block (resnet.py:269-271) -- as a second output of the same launch,
+ *     out  = as tfimm_hip_conv_chain computes it from `chain`                [M][N2]   bit-identical to that call
+ *     out2 = relu( out . W3^T + b3 )                                         [M][N3]
+ * so that convolution never re-reads the N2-channel tensor from memory: every slice of `out` is multiplied with W3 where it
+ * is formed, from the bf16 values that are stored (fp32 accumulation over all N2 channels, one rounding to bf16 -- the
+ * arithmetic of tfimm_hip_gemm on `out`, in another summation order).  w3: bf16 [N3][ldw3], K = N2 in natural order, BN
+ * folded; b3: fp32 [N3]; out2: bf16 rows of ldc2 elements (a multiple of 8).  Built for the plain stage-1 tail: C1 = 64,
+ * N2 = 256, N3 = 64, relu activations, no shortcut convolution (ds_x NULL).  TFIMM_EUNSUP for C1 = 128, the ds_* flavour,
+ * other activations and any other N2 / N3: the caller then runs tfimm_hip_conv_chain and tfimm_hip_gemm.
+ * A new entry point and a new descriptor: nothing that existed changed, the ABI version stays as it is.
+ * ------------------------------------------------------------------------------------- */
+typedef struct tfimm_chain_next_desc {
+  tfimm_chain_desc chain;
+  const void* w3;
+  const float* b3;
+  void* out2;
+  int32_t N3, ldw3, ldc2;
+} tfimm_chain_next_desc;
+
+TFIMM_API int tfimm_hip_conv_chain_next(const tfimm_chain_next_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * tfimm_hip_expand_dwconv: the front half of an inverted-residual block in one launch --
  *   conv_pw (1x1, Cin -> C) + bn1 + act1, then conv_dw (k x k depthwise, stride) + bn2 + act2, optionally the
  *   squeeze sums of the result (efficientnet_blocks.py:438-445, InvertedResidual.call up to `se`).

@@ -48,6 +48,11 @@ struct ChainArgs {
   const bf16_t* ds_x;       // DS flavour: the block input [M][64] whose 1x1 convolution IS the shortcut (resnet.py:315-330)
   const uint4* ds_w;        // DS flavour: its weights as MFMA fragments [N2 / 32][4][64 lanes][8] (pack.pack_chain_ds)
   bf16_t* out;              // [M][ldc]
+  const bf16_t* w3;         // NEXT flavour: the following block's conv1 kernel [64][ldw3] bf16 (BN folded), K = N2 in natural order
+  const float* b3;          // NEXT flavour: [64]
+  bf16_t* out2;             // NEXT flavour: [M][ldc2] = relu(out . W3^T + b3)
+  int ldw3, ldc2;
+  unsigned w3_bytes, out2_bytes;
   int M, N2;
   int B, H, W;
   int ldw1, ldw2, ldr, ldc;
@@ -95,9 +100,18 @@ struct ChainIdx {
 // its 256-channel result as the residual, the four extra k-steps  W_ds . x0  accumulate into the SAME accumulators as GEMM 2
 // (operands straight from global memory into registers: 16 bytes of x0 per lane and k-step once per tile, the weight fragments
 // per slice), so that launch and its tensor disappear; its folded-BN shift is added to b2 on the host.
-template <int NS2, int ACT = -1, bool DS = false>
+// NEXT: the 1x1 convolution that reads this block's output -- conv1 of the following block, N2 -> 64 channels, relu -- is a
+// third GEMM of the launch, so that convolution never re-reads the N2-channel tensor from memory.  A slice's final bf16 values
+// (the ones stored) go back into the first half of the wave's own staging block -- dead once the pass has read it -- as a
+// [32 pixels][64 channels] image in the lds_slot layout, and are read back as the B operand of four more k-steps; the matching
+// W3 slice [64][64] comes through the ring as a step of its own behind every W2 slice (the tile program is 9 taps, then
+// W2[0], W3[0], W2[1], W3[1], ...).  The two accumulator blocks live across the slices of a tile; behind the last slice they
+// take + b3, relu and one rounding through the same staging block to the second output.
+template <int NS2, int ACT = -1, bool DS = false, bool NEXT = false>
 __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
   using G = ChainGeom;
+  static_assert(!NEXT || (!DS && ACT == TFIMM_ACT_RELU && G::WTN == 64), "NEXT: plain flavour, relu compiled in, one 64-column pass");
+  constexpr int NXT = NEXT ? 1 : 0;
   constexpr int BM = G::BM, NW = G::NW, STAGE = G::STAGE, BN2 = G::BN2, NST = G::NST;
   constexpr int TN1 = 2;                           // GEMM-1 accumulator blocks per wave (32 pixels x 64)
   constexpr int STRIP_INSTR = G::STRIP_ROWS / 8 / NW;   // strip DMA pieces per wave (8)
@@ -134,8 +148,11 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
   const __amdgpu_buffer_rsrc_t rsrc_w2 = make_rsrc(p.w2, p.w2_bytes);
   const __amdgpu_buffer_rsrc_t rsrc_o = make_rsrc(p.out, p.out_bytes);
   const __amdgpu_buffer_rsrc_t rsrc_r = DS ? make_rsrc(p.ds_x, p.ds_bytes) : make_rsrc(p.residual, p.res_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_w3 = NEXT ? make_rsrc(p.w3, p.w3_bytes) : rsrc_w2;
+  const __amdgpu_buffer_rsrc_t rsrc_o2 = NEXT ? make_rsrc(p.out2, p.out2_bytes) : rsrc_o;
 
   static_assert(NS2 >= 2, "the counted waits below are derived for at least two GEMM-2 steps");
+  constexpr int T = NK1 + NS2 * (1 + NXT);         // weight steps of a tile: the taps, then per slice W2 (and W3 behind it)
   constexpr int LOOK = NST - 1;
   const int lrow = lane >> 3, lpc = lane & 7;
 
@@ -152,6 +169,12 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
   for (int j = 0; j < B2_INSTR; ++j) {
     const int r = (wave * B2_INSTR + j) * 8 + lrow;             // row within the 128-row slice
     b2_off[j] = (unsigned)(((size_t)r * p.ldw2 + (lpc ^ ((r >> 1) & 7)) * 8) * 2);
+  }
+  unsigned b3_off[B2_INSTR];                                    // NEXT: row of W3 = output channel of the following conv1
+#pragma unroll
+  for (int j = 0; j < B2_INSTR; ++j) {
+    const int r = (wave * B2_INSTR + j) * 8 + lrow;
+    b3_off[j] = NEXT ? (unsigned)(((size_t)r * p.ldw3 + (lpc ^ ((r >> 1) & 7)) * 8) * 2) : 0u;
   }
 #pragma unroll
   for (int j = 0; j < STRIP_INSTR; ++j) {
@@ -171,13 +194,13 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr_t)(smem + (wave * STRIP_INSTR + j) * 1024), 16, (int)off, 0, 0, 0);
     }
   };
-  // Weight step S of the tile being multiplied (S >= NK1 + NS2: a tap of this workgroup's NEXT tile) -> ring stage
+  // Weight step S of the tile being multiplied (S >= T: a tap of this workgroup's NEXT tile) -> ring stage
   // `iss_stage`.  S is a compile-time index: no VMEM operation inside a branch.
   int iss_stage = 0;
   auto issue_step = [&](auto sc, int tile) __attribute__((always_inline)) {
     constexpr int S = decltype(sc)::value;
-    constexpr int SL = S >= NK1 + NS2 ? S - NK1 - NS2 : S;          // index within its own tile's program
-    const bool valid = S >= NK1 + NS2 ? (tile + t_step < t_hi) : true;
+    constexpr int SL = S >= T ? S - T : S;                          // index within its own tile's program
+    const bool valid = S >= T ? (tile + t_step < t_hi) : true;
     char* const sa = sRing + iss_stage * STAGE;
     if constexpr (SL < NK1) {
 #pragma unroll
@@ -185,8 +208,14 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
         const unsigned off = valid ? b1_off[j] : kOobOffset;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w1, (lds_ptr_t)(sa + (wave * B1_INSTR + j) * 1024), 16, (int)off, SL * 128, 0, 0);
       }
+    } else if constexpr (NEXT && ((SL - NK1) & 1)) {
+      // columns 64 u .. 64 u + 63 of W3 (u = (SL - NK1) / 2): the k range slice u of the block output covers
+#pragma unroll
+      for (int j = 0; j < B2_INSTR; ++j)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w3, (lds_ptr_t)(sa + (wave * B2_INSTR + j) * 1024), 16, (int)b3_off[j],
+                                                 ((SL - NK1) / 2) * 128, 0, 0);
     } else {
-      const int soff = (int)((size_t)(SL - NK1) * BN2 * p.ldw2 * 2);
+      const int soff = (int)((size_t)((SL - NK1) / (1 + NXT)) * BN2 * p.ldw2 * 2);
 #pragma unroll
       for (int j = 0; j < B2_INSTR; ++j)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w2, (lds_ptr_t)(sa + (wave * B2_INSTR + j) * 1024), 16, (int)b2_off[j], soff, 0, 0);
@@ -212,31 +241,48 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
   // a slice: residual / bias of the NEXT slice, weight DMA, the next tile's strip behind slice 0, its own stores).
   // VMEM retires in issue order, so "step s's weights have landed" == "at most N(s) operations outstanding" with N(s) =
   // everything issued behind that DMA: the rest of step s - 3 and all of steps s - 2 and s - 1.
+  // NEXT: position NK1 + 2 u is slice u, NK1 + 2 u + 1 the W3 step behind it, which issues only its weight DMA -- the last
+  // one of a tile also the two b3 loads in front of that DMA and the STORES3 stores of the second output behind it.
+  constexpr int STORES3 = NEXT ? ITS : 0, B3_LOADS = NEXT ? 2 : 0;
+  constexpr bool B1_TILE = DS || NEXT;        // bias1 fetched per tile (below)
   struct Ops {
     static constexpr int all(int r) {           // r = position in the tile program
-      if (DS && r == NK1 - 2) return B1_INSTR + TN1 * 4;      // DS: the GEMM-1 bias quads are fetched here, per tile
+      if (B1_TILE && r == NK1 - 2) return B1_INSTR + TN1 * 4; // DS, NEXT: the GEMM-1 bias quads are fetched here, per tile
       if (r < NK1 - 1) return B1_INSTR;
       if (r == NK1 - 1) return EPI_LOADS + DS_X + B1_INSTR;
-      const int u = r - NK1;
+      const int u = (r - NK1) / (1 + NXT);
+      if (NEXT && ((r - NK1) & 1)) return u == NS2 - 1 ? B3_LOADS + B2_INSTR + STORES3 : B2_INSTR;
       return (u < NS2 - 1 ? EPI_LOADS : 0) + DS_W + B2_INSTR + (u == 0 ? STRIP_INSTR : 0) + STORES;
     }
     static constexpr int behind_dma(int r) {    // what step r issues after its weight DMA
       if (r < NK1) return 0;
-      return (r - NK1 == 0 ? STRIP_INSTR : 0) + STORES;
+      const int u = (r - NK1) / (1 + NXT);
+      if (NEXT && ((r - NK1) & 1)) return u == NS2 - 1 ? STORES3 : 0;
+      return (u == 0 ? STRIP_INSTR : 0) + STORES;
     }
     static constexpr int wait_for(int r) {
-      constexpr int T = NK1 + NS2;
       int n = behind_dma((r + T - LOOK) % T);
       for (int i = 1; i < LOOK; ++i) n += all((r + T - i) % T);
       return n;
     }
+    static constexpr int max_wait() {
+      int m = 0;
+      for (int r = 0; r < T; ++r) m = wait_for(r) > m ? wait_for(r) : m;
+      return m;
+    }
   };
   static_assert(B1_INSTR == B2_INSTR, "every weight step is two pieces per wave");
-  static_assert(Ops::wait_for(NK1 + NS2 - 1) < 64, "vmcnt is a 6-bit counter");
+  static_assert(Ops::max_wait() < 64, "vmcnt is a 6-bit counter");
+  // LOOK = 1: a step's weights are requested by the step before it, so what may stay in flight is what that step issued behind
+  // its DMA -- a slice's stores (and the strip behind slice 0), nothing behind a tap or a W3 step but the last one's stores
+  static_assert(!NEXT || LOOK != 1 || (Ops::wait_for(0) == STORES3 && Ops::wait_for(NK1) == 0 && Ops::wait_for(NK1 + 1) == STRIP_INSTR + STORES &&
+                                       Ops::wait_for(NK1 + 2) == 0 && Ops::wait_for(NK1 + 3) == STORES && Ops::wait_for(T - 1) == STORES),
+                "NEXT: counted waits");
 
   // bias of GEMM 1 in the accumulator layout: lane owns channels j*32 + q*8 + fhi*4 .. +3
   // (DS flavour: these 32 registers are what pushes it over the budget while GEMM 2 and the shortcut fragments are live, so it
-  // fetches them per tile instead, behind tap 7 -- eight L2 hits that are back long before epilogue 1)
+  // fetches them per tile instead, behind tap 7 -- eight L2 hits that are back long before epilogue 1; so does the NEXT flavour,
+  // whose 32 registers of acc3 are live exactly where bias1 is not needed)
   f32x4 bias1[TN1][4];
   auto load_bias1 = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -247,7 +293,7 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
         bias1[j][q] = f32x4{b4.x, b4.y, b4.z, b4.w};
       }
   };
-  if constexpr (!DS) {
+  if constexpr (!B1_TILE) {
     load_bias1();
     // their values must be in registers before the counted waits below start leaving operations in flight
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(bias1[0][0]), "+v"(bias1[0][3]), "+v"(bias1[TN1 - 1][0]), "+v"(bias1[TN1 - 1][3])::"memory");
@@ -322,7 +368,7 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
       if constexpr (k < LOOK) { if (first) chain_wait_vm<(LOOK - 1) * B1_INSTR>(); else chain_wait_vm<Ops::wait_for(k)>(); }
       else chain_wait_vm<Ops::wait_for(k)>();
       tfimm_lds_reuse_barrier();       // (this wave's reads of the stage about to be refilled are complete: common.h)
-      if constexpr (DS && k == NK1 - 2) { load_bias1(); __builtin_amdgcn_sched_barrier(0); }
+      if constexpr (B1_TILE && k == NK1 - 2) { load_bias1(); __builtin_amdgcn_sched_barrier(0); }
       if constexpr (k == NK1 - 1) {
         load_epi(ChainIdx<0>{});
         if constexpr (DS) {
@@ -388,11 +434,19 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
       }
 
     // =========================== GEMM 2: 32 pixels x 64 channels per wave and step ===========================
+    f32x16 acc3[TN2];          // NEXT: the following conv1, 32 pixels x 64 channels, summed over the slices of this tile
     auto slice_step = [&](auto uc) __attribute__((always_inline)) {
       constexpr int u = decltype(uc)::value;
       constexpr int n0 = u * BN2;
+      constexpr int R = NK1 + u * (1 + NXT);       // position in the tile program
       const unsigned out_off0 = (unsigned)(((size_t)em * p.ldc + n0 + e_c8 * 8) * 2);
-      chain_wait_vm<Ops::wait_for(NK1 + u)>();
+      if constexpr (NEXT && u == 0) {
+#pragma unroll
+        for (int j = 0; j < TN2; ++j)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc3[j][e] = 0.f;
+      }
+      chain_wait_vm<Ops::wait_for(R)>();
       tfimm_lds_reuse_barrier();       // (this wave's reads of the stage about to be refilled are complete: common.h)
       if constexpr (u + 1 < NS2) load_epi(ChainIdx<u + 1>{});
       u32x4 wds[TN2][4];
@@ -403,7 +457,7 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
           for (int t = 0; t < 4; ++t) wds[j][t] = __builtin_bit_cast(u32x4, p.ds_w[(size_t)((u * TN2 + j) * 4 + t) * 64 + lane]);
       }
       __builtin_amdgcn_sched_barrier(0);      // keep every one of those loads ahead of the LDS-DMA in issue order
-      issue_step(ChainIdx<NK1 + u + LOOK>{}, tile);
+      issue_step(ChainIdx<R + LOOK>{}, tile);
       if constexpr (u == 0) issue_strip(tile + t_step, tile + t_step < t_hi);   // every wave has passed GEMM 1: the strip is free
       __builtin_amdgcn_sched_barrier(0);
 
@@ -485,17 +539,113 @@ __global__ void __launch_bounds__(256, 2) gemm_chain_kernel(const ChainArgs p) {
           act8p(v, act2p);
           const unsigned off = out_off0 + (unsigned)(it * RPI) * ldc2 + (unsigned)(g * WTN * 2);
           // every wave issues all STORES stores of a step (rows >= M fall off the descriptor): the counted waits rely on it
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pack8p(v)), rsrc_o,
-                                                 (int)(skip_epi ? kOobOffset : off), 0, 0);
+          const u32x4 pk = __builtin_bit_cast(u32x4, pack8p(v));
+          __builtin_amdgcn_raw_buffer_store_b128(pk, rsrc_o, (int)(skip_epi ? kOobOffset : off), 0, 0);
+          if constexpr (NEXT) {
+            // the same 8 values as chunk e_c8 of pixel row `pr` of the wave's bf16 image [32][64]: bytes 0 .. 4095 of the staging
+            // block, i.e. fp32 rows 0 .. 15, which the first read of this pass (ip = 0) has consumed (a wave's LDS operations
+            // execute in order; the second read takes rows 16 .. 31, bytes 4096 ..)
+            const int pr = it * RPI + e_row;
+            const unsigned addr = (unsigned)(size_t)(lds_ptr_t)(reinterpret_cast<char*>(sEw) + lds_slot(pr, e_c8) * 16);
+            asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(pk) : "memory");
+          }
         }
         }
       }
     };
+    // NEXT, behind slice u: acc3 += W3[:, 64 u .. 64 u + 63] . slice u of the block output, the latter read back from the wave's
+    // bf16 image as B fragments (lane: pixel frow, channels 16 t + 8 fhi .. + 7 of the slice: natural k order on both operands)
+    auto next_step = [&](auto uc) __attribute__((always_inline)) {
+      constexpr int u = decltype(uc)::value;
+      constexpr int R = NK1 + 2 * u + 1;
+      constexpr bool last = u == NS2 - 1;
+      chain_wait_vm<Ops::wait_for(R)>();
+      tfimm_lds_reuse_barrier();       // (this wave's reads of the stage about to be refilled are complete: common.h)
+      float4 b3raw[2];
+      if constexpr (last) {
+        b3raw[0] = *reinterpret_cast<const float4*>(p.b3 + e_c8 * 8);
+        b3raw[1] = *reinterpret_cast<const float4*>(p.b3 + e_c8 * 8 + 4);
+      }
+      __builtin_amdgcn_sched_barrier(0);      // keep those loads ahead of the LDS-DMA in issue order
+      issue_step(ChainIdx<R + LOOK>{}, tile);
+      __builtin_amdgcn_sched_barrier(0);
+      u32x4 ub[KS2];
+      {
+        unsigned ra[KS2];
+#pragma unroll
+        for (int t = 0; t < KS2; ++t) ra[t] = (unsigned)(size_t)(lds_ptr_t)(reinterpret_cast<char*>(sEw) + lds_slot(frow, t * 2 + fhi) * 16);
+        asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(ub[0]), "=&v"(ub[1]), "=&v"(ub[2]), "=&v"(ub[3])
+                     : "v"(ra[0]), "v"(ra[1]), "v"(ra[2]), "v"(ra[3]) : "memory");
+      }
+      {
+        const uint4* sW = reinterpret_cast<const uint4*>(sRing + cur * STAGE);
+#pragma unroll
+        for (int t = 0; t < KS2; ++t) {
+          bf16x8 fw[TN2];
+#pragma unroll
+          for (int j = 0; j < TN2; ++j) fw[j] = __builtin_bit_cast(bf16x8, sW[lds_slot(j * 32 + frow, t * 2 + fhi)]);
+#pragma unroll
+          for (int j = 0; j < TN2; ++j)
+            acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[j], __builtin_bit_cast(bf16x8, ub[t]), acc3[j], 0, 0, 0);
+        }
+      }
+      rotate();
+      if constexpr (last) {
+        // ---- epilogue 3: + b3, relu, bf16 -> out2 rows of 64 channels, through the same staging block as epilogue 2
+        const unsigned out2_off0 = (unsigned)(((size_t)em * p.ldc2 + e_c8 * 8) * 2);
+        const unsigned ldc22 = (unsigned)p.ldc2 * 2u;
+        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc3[0]), "+v"(acc3[TN2 - 1]));
+#pragma unroll
+        for (int j = 0; j < TN2; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int slot = j * 8 + q * 2 + fhi;
+            const f32x4 v = {acc3[j][q * 4 + 0], acc3[j][q * 4 + 1], acc3[j][q * 4 + 2], acc3[j][q * 4 + 3]};
+            const unsigned addr = (unsigned)(size_t)(lds_ptr_t)(&sEw[frow * WTN + epi_slot(frow, slot) * 4]);
+            asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
+          }
+        const tfimm_f32x2 bias3[4] = {{b3raw[0].x, b3raw[0].y}, {b3raw[0].z, b3raw[0].w}, {b3raw[1].x, b3raw[1].y}, {b3raw[1].z, b3raw[1].w}};
+#pragma unroll
+        for (int ip = 0; ip < ITS; ip += 2) {
+          f32x4 st[4];
+          {
+            unsigned ra[4];
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+              const int pr = (ip + w) * RPI + e_row;
+              ra[2 * w] = (unsigned)(size_t)(lds_ptr_t)(&sEw[pr * WTN + epi_slot(pr, 2 * e_c8) * 4]);
+              ra[2 * w + 1] = (unsigned)(size_t)(lds_ptr_t)(&sEw[pr * WTN + epi_slot(pr, 2 * e_c8 + 1) * 4]);
+            }
+            asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\t"
+                         "s_waitcnt lgkmcnt(0)"
+                         : "=&v"(st[0]), "=&v"(st[1]), "=&v"(st[2]), "=&v"(st[3])
+                         : "v"(ra[0]), "v"(ra[1]), "v"(ra[2]), "v"(ra[3]) : "memory");
+          }
+#pragma unroll
+          for (int w = 0; w < 2; ++w) {
+            const int it = ip + w;
+            const f32x4 lo = st[2 * w], hi = st[2 * w + 1];
+            tfimm_f32x2 v[4] = {{lo[0], lo[1]}, {lo[2], lo[3]}, {hi[0], hi[1]}, {hi[2], hi[3]}};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] += bias3[e];
+            act8p(v, act2p);
+            // every wave issues all STORES3 stores (rows >= M fall off the descriptor): the counted waits rely on it
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pack8p(v)), rsrc_o2,
+                                                   (int)(out2_off0 + (unsigned)(it * RPI) * ldc22), 0, 0);
+          }
+        }
+      }
+    };
     slice_step(ChainIdx<0>{});
+    if constexpr (NEXT) next_step(ChainIdx<0>{});
     slice_step(ChainIdx<1>{});
-    if constexpr (NS2 > 2) slice_step(ChainIdx<2>{});
-    if constexpr (NS2 > 3) slice_step(ChainIdx<3>{});
+    if constexpr (NEXT) next_step(ChainIdx<1>{});
+    if constexpr (NS2 > 2) { slice_step(ChainIdx<2>{}); if constexpr (NEXT) next_step(ChainIdx<2>{}); }
+    if constexpr (NS2 > 3) { slice_step(ChainIdx<3>{}); if constexpr (NEXT) next_step(ChainIdx<3>{}); }
     if constexpr (NS2 > 4) { slice_step(ChainIdx<4>{}); slice_step(ChainIdx<5>{}); slice_step(ChainIdx<6>{}); slice_step(ChainIdx<7>{}); }
+    static_assert(!NEXT || NS2 <= 4, "NEXT is instantiated for N2 = 256");
     static_assert(NS2 == 2 || NS2 == 3 || NS2 == 4 || NS2 == 8, "instantiate the slice steps of this NS2");
     first = false;
   }

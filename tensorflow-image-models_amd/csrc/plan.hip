@@ -92,6 +92,7 @@ const std::map<std::string, Entry>& table() {
   static const std::map<std::string, Entry> t = {
       TFIMM_ADAPTER_DESC(tfimm_hip_gemm, tfimm_gemm_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_conv_chain, tfimm_chain_desc),
+      TFIMM_ADAPTER_DESC(tfimm_hip_conv_chain_next, tfimm_chain_next_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_mlp_fused, tfimm_mlp_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_gemm_mx, tfimm_gemm_mx_desc),
       TFIMM_ADAPTER_DESC(tfimm_hip_expand_dwconv, tfimm_expand_dw_desc),

@@ -86,6 +86,15 @@ class ChainDesc(C.Structure):
     ]
 
 
+class ChainNextDesc(C.Structure):
+    """tfimm_chain_next_desc: the fields of tfimm_chain_desc (its first member ``chain``, written flat here so that
+    Plan.export finds every pointer), then the following block's conv1 as a second output of the launch"""
+    _fields_ = ChainDesc._fields_ + [
+        ("w3", C.c_void_p), ("b3", C.c_void_p), ("out2", C.c_void_p),
+        ("N3", C.c_int32), ("ldw3", C.c_int32), ("ldc2", C.c_int32),
+    ]
+
+
 class ExpandDwDesc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("wdw", C.c_void_p), ("b2", C.c_void_p),
@@ -214,6 +223,7 @@ SYMBOLS = {
     "tfimm_hip_device_info": (_i, [_i, C.c_char_p, _i]),
     "tfimm_hip_gemm": (_i, [C.POINTER(GemmDesc), _vp]),
     "tfimm_hip_conv_chain": (_i, [C.POINTER(ChainDesc), _vp]),
+    "tfimm_hip_conv_chain_next": (_i, [C.POINTER(ChainNextDesc), _vp]),
     "tfimm_hip_mlp_fused": (_i, [C.POINTER(MlpDesc), _vp]),
     "tfimm_hip_gemm_mx": (_i, [C.POINTER(GemmMxDesc), _vp]),
     "tfimm_hip_quantize_mx": (_i, [_vp, _i64, _i, _i64, _vp, _vp, _f, _vp, _vp, _i, _vp]),

@@ -136,10 +136,37 @@ class Program:
         return sum(c.nbytes for c in self.consts)
 
     # -- buffer planning ---------------------------------------------------------------------
-    def plan_buffers(self) -> Tuple[Dict[int, int], List[int]]:
+    def chain_next_pairs(self, split_at: Optional[int] = None) -> List[int]:
+        """Indices i of fused bottleneck tails whose successor op i + 1 is the 1x1 convolution tfimm_hip_conv_chain_next
+        computes as a second output of the tail's launch: the plain relu flavour with 64 -> 256 channels (residual or not, no
+        shortcut convolution), followed by a dense GEMM over exactly its output, 256 -> 64 channels, bias, relu, nothing else in
+        its epilogue -- conv1 + bn1 + act of the next bottleneck block (resnet.py:269-271).  A plan launches such a pair once;
+        the program keeps both ops.  ``split_at``: an op index at which a recording is cut into parts (CapturedHybrid): the
+        pair that straddles it stays two launches.  TFIMM_NO_CHAIN_NEXT=1: none (A/B)."""
+        if self.precision == "fp32" or os.environ.get("TFIMM_NO_CHAIN_NEXT", "0") == "1":
+            return []
+        pairs = []
+        for i in range(len(self.ops) - 1):
+            c, g = self.ops[i], self.ops[i + 1]
+            ca, ga = c.attrs, g.attrs
+            if (c.kind != "conv_chain" or g.kind != "gemm" or i + 1 == split_at or c.extra_outputs
+                    or (ca["C1"], ca["N2"], ca["act1"], ca["act2"]) != (64, 256, "relu", "relu") or ca.get("has_ds")):
+                continue
+            if (g.inputs != [c.output] or ga.get("mode") != 0 or (ga["K"], ga["N"], ga["ldw"], ga["lda"]) != (256, 64, 256, 256)
+                    or ga["act"] != "relu" or ga["out_f32"] or "bias" not in g.consts or set(g.consts) - {"wt", "bias"}
+                    or any(ga.get(k) for k in ("has_residual", "has_scale", "remap", "dual", "res_mod", "ln", "a_byte_offset", "out_col",
+                                                 "out_byte_offset", "ldc"))
+                    or ga["M"] != ca["OH"] * ca["OW"] or self.tensors[g.output].C != 64):
+                continue
+            pairs.append(i)
+        return pairs
+
+    def plan_buffers(self, fused=()) -> Tuple[Dict[int, int], List[int]]:
         """Greedy liveness-based slab assignment.  Returns (tensor id -> slab, slab bytes
         per image).  A tensor's slab is recycled after its last reader; outputs of an op are
-        placed before its inputs are released, so a kernel never reads and writes one slab."""
+        placed before its inputs are released, so a kernel never reads and writes one slab.
+        ``fused``: op indices i whose launch also writes the output of op i + 1 (chain_next_pairs): that tensor is placed with
+        op i's own output, before op i's inputs are released."""
         last_use: Dict[int, int] = {}
         for i, op in enumerate(self.ops):
             for t in op.inputs:
@@ -151,6 +178,8 @@ class Program:
         assign: Dict[int, int] = {}
         for i, op in enumerate(self.ops):
             outs = ([op.output] if op.output is not None else []) + op.extra_outputs
+            if i in fused:
+                outs = outs + [self.ops[i + 1].output]
             for out in outs:
                 if out in assign:
                     continue
@@ -1216,11 +1245,14 @@ def _grown(need: int, have: int, floor: int) -> int:
 # Plan: a program bound to device buffers for one batch size
 # ---------------------------------------------------------------------------------------
 class Plan:
-    def __init__(self, prog: Program, batch: int, device: str = "cuda", external: Optional[Dict[int, int]] = None):
+    def __init__(self, prog: Program, batch: int, device: str = "cuda", external: Optional[Dict[int, int]] = None,
+                 split_at: Optional[int] = None):
         """``device="cpu"`` builds the same call list over host buffers; it can only be used
         to inspect / marshal-check the plan (tests without a GPU) -- launching it fails.
         ``external``: tensor id -> device address: those tensors live at that address instead of in this plan's slabs (the
-        branches of ``CapturedHybrid`` write what crosses the join straight into the full-batch plan's buffers)."""
+        branches of ``CapturedHybrid`` write what crosses the join straight into the full-batch plan's buffers).
+        ``split_at``: the op index at which the caller cuts the call list into parts run by different plans: no launch of this
+        plan covers ops on both sides of it (Program.chain_next_pairs)."""
         import torch
         from . import ffi
         self.ffi = ffi
@@ -1230,7 +1262,9 @@ class Plan:
         self.batch = batch
         self.device = device
         prog.upload(device)
-        assign, slabs = prog.plan_buffers()
+        #: tails launched together with the 1x1 convolution behind them (tfimm_hip_conv_chain_next): op i + 1 has no call of its own
+        self.fused_next = frozenset(prog.chain_next_pairs(split_at))
+        assign, slabs = prog.plan_buffers(self.fused_next)
         self.slab_bytes = [s * batch for s in slabs]
         self.slabs = [torch.empty(max(n, 16), dtype=torch.uint8, device=device) for n in self.slab_bytes]
         self.assign = assign
@@ -1289,10 +1323,12 @@ class Plan:
     def _build(self):
         ffi, lib, B = self.ffi, self.ffi.lib, self.batch
         prog = self.prog
-        for op in prog.ops:
+        for oi, op in enumerate(prog.ops):
             a = op.attrs
             k = op.kind
             self.op_call_start.append(len(self.calls))
+            if oi - 1 in self.fused_next:      # computed by the previous op's launch
+                continue
             if k == "cast_input":
                 out = self.tptr(op.output)
                 H, W, cin = prog.input_shape
@@ -1390,7 +1426,8 @@ class Plan:
                 self._keepalive.append(d)
                 self.calls.append((lib.tfimm_hip_gemm_mx, (C.byref(d),)))
             elif k == "conv_chain":
-                d = ffi.ChainDesc()
+                nxt = prog.ops[oi + 1] if oi in self.fused_next else None
+                d = ffi.ChainNextDesc() if nxt is not None else ffi.ChainDesc()
                 d.x = self.tptr(op.inputs[0])
                 d.w1, d.b1 = self.cptr(op.consts["w1"]), self.cptr(op.consts["b1"])
                 d.w2, d.b2 = self.cptr(op.consts["w2"]), self.cptr(op.consts["b2"])
@@ -1403,7 +1440,12 @@ class Plan:
                 d.C1, d.N2, d.ldw1, d.ldw2, d.ldr, d.ldc = a["C1"], a["N2"], a["ldw1"], a["ldw2"], a["N2"], a["N2"]
                 d.act1, d.act2 = ffi.ACT[a["act1"]], ffi.ACT[a["act2"]]
                 self._keepalive.append(d)
-                self.calls.append((lib.tfimm_hip_conv_chain, (C.byref(d),)))
+                if nxt is not None:      # the 1x1 convolution behind the tail: its packed weights, bias and output as they are
+                    d.w3, d.b3, d.out2 = self.cptr(nxt.consts["wt"]), self.cptr(nxt.consts["bias"]), self.tptr(nxt.output)
+                    d.N3, d.ldw3, d.ldc2 = nxt.attrs["N"], nxt.attrs["ldw"], prog.tensors[nxt.output].C
+                    self.calls.append((lib.tfimm_hip_conv_chain_next, (C.byref(d),)))
+                else:
+                    self.calls.append((lib.tfimm_hip_conv_chain, (C.byref(d),)))
             elif k == "mlp_fused":
                 d = ffi.MlpDesc()
                 d.x, d.residual, d.out = self.tptr(op.inputs[0]), self.tptr(op.inputs[1]), self.tptr(op.output)
@@ -2160,13 +2202,17 @@ class Plan:
 
     def _roctx_labels(self) -> List[str]:
         """One label per entry of ``self.calls``: the op it belongs to (memsets sit in front of their op)."""
-        labels, ops = [], iter(self.prog.ops)
+        labels, ops = [], iter(enumerate(self.prog.ops))
         for fn, _ in self.calls:
             if fn == "memset":
                 labels.append("memset (squeeze sums)")
                 continue
-            op = next(ops)
-            labels.append(f"{len(labels)} {op.kind} {op.cite}".strip())
+            oi, op = next(ops)
+            label = f"{len(labels)} {op.kind} {op.cite}"
+            if oi in self.fused_next:      # one launch for this op and the next
+                nxt = next(ops)[1]
+                label += f" + {nxt.kind} {nxt.cite}"
+            labels.append(label.strip())
         return labels
 
 
@@ -2253,14 +2299,14 @@ class CapturedHybrid:
         import torch
         B = x_dev.shape[0]
         assert 0 < cut_op <= len(prog.ops) and B >= 2
-        self.full = Plan(prog, B)
+        self.full = Plan(prog, B, split_at=cut_op)
         nb = branch_sizes(B, 2)
         live = prog.live_across(cut_op) if cut_op < len(prog.ops) else [t.id for t in prog.tensors if t.keep and t.dtype != "raw"]
         live = [t for t in live if prog.tensors[t].dtype != "raw"]
         self.halves, lo = [], 0
         for n_img in nb:
             ext = {t: self.full.tptr(t) + lo * prog.tensors[t].bytes_per_image for t in live}
-            self.halves.append(Plan(prog, n_img, external=ext))
+            self.halves.append(Plan(prog, n_img, external=ext, split_at=cut_op))
             lo += n_img
         self.static_input = x_dev
         self.cut_op = cut_op

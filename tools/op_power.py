@@ -51,9 +51,10 @@ def main():
     for i, (fn, args) in enumerate(plan.calls):
         if fn == "memset":
             continue
+        nxt = prog.ops[oi + 1] if oi in plan.fused_next else None       # a tail launched with the convolution behind it
         op = prog.ops[oi]
-        oi += 1
-        byts, flops, desc = op_bytes_flops(op, prog, B)
+        oi += 2 if nxt is not None else 1
+        byts, flops, desc = op_bytes_flops(op, prog, B, nxt)
         key = (op.kind, desc)
         if key not in groups:
             if i == idx:

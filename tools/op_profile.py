@@ -17,7 +17,8 @@ for p in (ROOT, os.path.join(ROOT, "tensorflow-image-models_amd"), os.path.join(
 import torch  # noqa: E402
 
 
-def op_bytes_flops(op, prog, B):
+def op_bytes_flops(op, prog, B, nxt=None):
+    """``nxt``: the op behind a fused bottleneck tail that the plan computes in the tail's launch (Plan.fused_next)"""
     a = op.attrs
     tin = [prog.tensors[i] for i in op.inputs]
     tout = prog.tensors[op.output] if op.output is not None else None
@@ -60,9 +61,15 @@ def op_bytes_flops(op, prog, B):
             byts += M * a["N2"] * 2
         if a.get("has_ds"):
             byts += M * a["Cin"] * 2 + a["N2"] * a["Cin"] * 2
-        return byts, float(a["flops"]) * B, (f"M={M} 3x3 {a['Cin']}->{a['C1']} -> 1x1 ->{a['N2']}" +
-                                             (" +res" if a.get("has_residual") else "") +
-                                             (" +shortcut conv" if a.get("has_ds") else "") + " (fused bottleneck tail)")
+        flops = float(a["flops"]) * B
+        if nxt is not None:     # + the next block's conv1: its weights and its output; its input never leaves the chip
+            na = nxt.attrs
+            byts += M * na["N"] * 2 + na["N"] * na["ldw"] * 2
+            flops += 2.0 * M * na["N"] * na["K_true"]
+        return byts, flops, (f"M={M} 3x3 {a['Cin']}->{a['C1']} -> 1x1 ->{a['N2']}" +
+                             (" +res" if a.get("has_residual") else "") +
+                             (" +shortcut conv" if a.get("has_ds") else "") +
+                             (f" -> next 1x1 ->{nxt.attrs['N']}" if nxt is not None else "") + " (fused bottleneck tail)")
     if k == "mlp_fused":
         M = B * a["rows"]
         byts = M * a["C"] * 2 * (3 if op.inputs[0] != op.inputs[1] else 2) + 2 * a["C"] * a["hidden"] * 2
@@ -95,20 +102,21 @@ def main():
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     idx = plan._input_patch[0]
     oi = 0
-    # map calls -> ops (memset calls belong to the following dwconv)
+    # map calls -> ops (memset calls belong to the following dwconv; a tail in plan.fused_next also computes the op behind it)
     call_ops = []
     for fn, args in plan.calls:
         if fn == "memset":
             call_ops.append(None)
         else:
-            call_ops.append(prog.ops[oi])
-            oi += 1
+            fused = oi in plan.fused_next
+            call_ops.append((prog.ops[oi], prog.ops[oi + 1] if fused else None))
+            oi += 2 if fused else 1
     rows = []
     tot = 0.0
     for i, (fn, args) in enumerate(plan.calls):
         if fn == "memset":
             continue
-        op = call_ops[i]
+        op, nxt = call_ops[i]
 
         def launch():
             if i == idx:
@@ -123,7 +131,7 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / iters
-        byts, flops, desc = op_bytes_flops(op, prog, B)
+        byts, flops, desc = op_bytes_flops(op, prog, B, nxt)
         rows.append((op.kind, desc, ms, byts, flops))
         tot += ms
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
