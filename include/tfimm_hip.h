@@ -1177,6 +1177,43 @@ TFIMM_API int tfimm_hip_embed_search_coarse(const float* q, int64_t ld_q, int B,
                                             int64_t ld_c, const int8_t* exps, int N, int E, int k, int candidates, int chunk,
                                             float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* tfimm_hip_embed_search_lists (csrc/embed_lists.hip; the CPU restatement of the rule is tests/index_ref.py): the
+ * gallery search over INVERTED LISTS -- only the rows of the lists a query names are scored.  The caller holds the index:
+ *   g       bf16  [N][ld_g]  the gallery rows IN LIST ORDER: list l is positions offsets[l] : offsets[l + 1]
+ *   ids     int32 [N]        the original row of every position, ascending inside a list
+ *   offsets int32 [L + 1]    ascending (a CSR form)
+ *   probes  int32 [B][ld_p]  per query the nprobe lists to search; an entry outside [0, L) (-1: "no list") contributes nothing
+ * q, scores, indices as for tfimm_hip_embed_search.  The candidates of a query are the rows of its lists; the result is the k
+ * best of them by score descending, equal scores by ascending ORIGINAL row (indices holds ids, not positions), the score
+ * being sum_e q16[b][e] * row[e] from the loop of tfimm_hip_embed_search (csrc/embed_score.h): a returned score has the bits
+ * that entry point gives for that row.  Where the lists hold fewer than k rows the remaining slots hold index -1 and score
+ * -inf.  The lists of one query are meant to be distinct; a list named more than once counts ONCE (every later entry that
+ * repeats an earlier one of the same query is "no list"), so a row is never returned twice.
+ * Out-of-range input does not fault: offsets are clamped to [0, N], a list whose end is below its begin is empty, ids are
+ * copied and never used as an address.  The order is specified for ids that ascend inside every list.
+ * Two launches on `stream`.  Pass 1, grid (nprobe * parts, B): one workgroup scores the p-th of `parts` equal cuts
+ * (ceil(len / parts) rows each) of one list against one query held in LDS as bf16, keeps ONE unsorted buffer of k + 256
+ * (key, position) pairs with a threshold (csrc/embed_buffer.h; the step structure of tfimm_hip_embed_search_wide) and leaves
+ * its k best, with ids in place of positions, in `workspace`; it also writes the query's outputs as "none".  LDS is
+ * 2 E + 16 + 8 (k + 256) bytes, about 8 KiB at most: many workgroups per CU.  Pass 2 merges the nprobe * parts * k pairs of a
+ * query and orders the survivors by rank, as in tfimm_hip_embed_search_wide.
+ * The result does not depend on B, on parts, on which queries share a call or on timing; bit-reproducible, no float atomics,
+ * no scratch memory, no allocation, capturable; offsets are 64-bit.
+ * parts == 0: the library chooses (1: it does not know the lists' lengths; the caller who does passes about len / 2048 of the
+ * longest list).
+ * Limits: E, ld_q, ld_g and alignment as for tfimm_hip_embed_search; 1 <= N < 2^31; 1 <= k <= TFIMM_EMBED_WIDE_MAX_K (k may
+ * exceed the rows probed, and N); 1 <= nprobe <= TFIMM_EMBED_LISTS_MAX_PROBE; ld_p >= nprobe; 1 <= L <= TFIMM_CLUSTER_MAX_C;
+ * 0 <= parts <= 64; 0 <= B <= 65535 (B is a grid dimension; nprobe * parts, the other, is at most 16384); ids / offsets / probes 4-byte aligned;
+ * workspace_bytes >= tfimm_hip_embed_search_lists_workspace(B, N, E, L, nprobe, k, parts) = max(B, 1) * nprobe * parts * k * 8
+ * (TFIMM_EINVAL, negative, for arguments the search would refuse).  Everything else is TFIMM_EINVAL before any launch, with a
+ * message naming the argument.  B == 0 returns 0 and launches nothing. */
+#define TFIMM_EMBED_LISTS_MAX_PROBE 256
+TFIMM_API int64_t tfimm_hip_embed_search_lists_workspace(int B, int N, int E, int L, int nprobe, int k, int parts);
+TFIMM_API int tfimm_hip_embed_search_lists(const float* q, int64_t ld_q, int B, const void* g, int64_t ld_g, int N, int E,
+                                           const int32_t* ids, const int32_t* offsets, int L, const int32_t* probes, int64_t ld_p,
+                                           int nprobe, int k, int parts, float* scores, int32_t* indices, void* workspace,
+                                           int64_t workspace_bytes, void* stream);
+
 /* =======================================================================================
  * KNN END (csrc/knn.hip; the CPU restatement of the rule is tests/knn_ref.py): the matches of a gallery
  * search turned into classes through a label per gallery row, in one launch behind tfimm_hip_embed_search.

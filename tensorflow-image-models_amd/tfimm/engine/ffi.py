@@ -292,6 +292,10 @@ SYMBOLS = {
     "tfimm_hip_embed_search_coarse_max_candidates": (_i, [_i]),
     "tfimm_hip_embed_search_coarse_workspace": (_i64, [_i, _i, _i, _i, _i, _i]),
     "tfimm_hip_embed_search_coarse": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    # the search over inverted lists (csrc/embed_lists.hip): B, N, E, L, nprobe, k, parts |
+    # q, ld_q, B, g, ld_g, N, E, ids, offsets, L, probes, ld_p, nprobe, k, parts, scores, indices, workspace, workspace_bytes
+    "tfimm_hip_embed_search_lists_workspace": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "tfimm_hip_embed_search_lists": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     # the kNN end (csrc/knn.hip): indices, scores, ld, B, k, glabels, N, exclude, inv_temperature, then
     # reduce, top, classes, values, counts, total | nb_classes, labels, loss, rank, pred, prob, state, per_class, confusion
     "tfimm_hip_knn_vote": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -438,6 +442,9 @@ EMBED_MIN_E, EMBED_MAX_E, EMBED_MAX_K = 16, 2048, 64
 EMBED_MAX_B = 65535 * 32          # queries per call: tiles of 32 are one grid dimension
 EMBED_WIDE_MAX_K = 256            # tfimm_hip_embed_search_wide; what a width E allows: tfimm_hip_embed_search_wide_max_k(E)
 EMBED_COARSE_MAX_CANDIDATES = 256 # tfimm_hip_embed_search_coarse; per width: tfimm_hip_embed_search_coarse_max_candidates(E)
+EMBED_LISTS_MAX_PROBE = 256       # tfimm_hip_embed_search_lists: lists per query
+EMBED_LISTS_MAX_PARTS = 64        # ... and cuts of a list, one workgroup each
+EMBED_LISTS_MAX_B = 65535         # ... and queries per call: one grid dimension
 # include/tfimm_hip.h: the domain of tfimm_hip_knn_vote / tfimm_hip_knn_score (one lane per candidate and per slot of the list)
 KNN_MAX_K, KNN_MAX_TOP, KNN_SUM, KNN_MAX = EMBED_MAX_K, 64, 0, 1
 # include/tfimm_hip.h: centroids per tfimm_hip_cluster_assign; entries per run of tfimm_hip_segment_mean's summation rule

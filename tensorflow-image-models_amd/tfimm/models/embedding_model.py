@@ -182,6 +182,15 @@ class EmbeddingModel(Model):
         gallery._coarse_args(k, candidates)
         return gallery.search_coarse(self._embeddings_for(x, gallery), k, candidates)
 
+    def search_index(self, x, index, k: int = 5, nprobe: int = 8):
+        """``index.search(model(x), k, nprobe)`` for a ``tfimm.GalleryIndex``: the model's recording, then the probe of the
+        centroids and the search of the probed lists, on the same stream; ``Matches(indices, scores)``, each (B, k).  Every
+        argument is checked before the forward pass runs."""
+        if index.dim != self.embed_dim:
+            raise ValueError(f"{self.name}: embeddings have {self.embed_dim} columns, the index holds rows of {index.dim}")
+        index._args(k, nprobe)
+        return index.search(self._embeddings_for(x, index), k, nprobe)
+
     def _embeddings_for(self, x, gallery):
         emb = self(x)
         if len(emb.shape) != 2:

@@ -4,7 +4,8 @@ csrc/embed_wide.hip; coarse to fine over an fp8 copy of the rows
 csrc/embed_coarse.hip); with a label per row, the matches turned into classes and
 scored on the device (tfimm_hip_knn_vote / tfimm_hip_knn_score, csrc/knn.hip); and the rows grouped on the
 device -- every row to its best centroid, the mean of every group -- into class prototypes and spherical k-means
-(tfimm_hip_cluster_assign / tfimm_hip_segment_mean, csrc/cluster.hip)."""
+(tfimm_hip_cluster_assign / tfimm_hip_segment_mean, csrc/cluster.hip).  ``build_index`` turns the groups into
+the inverted lists of a ``GalleryIndex`` (gallery_index.py), the one search that does not read every row."""
 import ctypes as C
 from collections import namedtuple
 
@@ -755,3 +756,15 @@ class Gallery:
         centroids = Gallery._of_rows(self.dim, cen[:, :self.dim].float(), torch.arange(k, dtype=torch.int32, device=dev))
         return Clusters(centroids, Tensor(a), Tensor(s), Tensor(counts), Tensor(moved))
 
+    # -- the inverted-list index over the k-means lists (gallery_index.py; csrc/embed_lists.hip) ----------------------
+    def build_index(self, n_lists=None, iters: int = 10, init=None, seed: int = 0, clusters=None):
+        """A ``tfimm.GalleryIndex`` over the rows the gallery holds now: ``kmeans(n_lists, iters, init, seed)`` groups them --
+        ``n_lists=None`` means ``round(sqrt(len))``, clamped to [1, TFIMM_CLUSTER_MAX_C]; or pass the ``Clusters`` of an earlier
+        ``kmeans`` as ``clusters`` --, and every group becomes an inverted list: a stable sort of the assignment,
+        ``searchsorted`` for the offsets and a gather of the rows, by ``torch`` on the device.  The index owns a list-ordered
+        copy of the bf16 rows, so it DOUBLES the gallery's memory.  One host synchronisation: the length of the longest list,
+        from which the search's workgroups per list are derived.  The index is a snapshot: rows added later are not in it
+        (``index.stale``) until a new build.  ``search``, ``classify`` and ``evaluate`` of the gallery are untouched and never
+        take the index: ``index.search(q, k, nprobe)`` does."""
+        from .gallery_index import build_index
+        return build_index(self, n_lists, iters, init, seed, clusters)

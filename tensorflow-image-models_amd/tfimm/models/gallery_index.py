@@ -1,0 +1,187 @@
+"""``GalleryIndex``: an inverted-list index over a ``Gallery`` -- the rows grouped by their best k-means centroid, and a search
+that scores only the lists a query probes (tfimm_hip_embed_search_lists, csrc/embed_lists.hip).  Every
+search path of ``Gallery`` reads the whole gallery; this one reads ``nprobe`` of ``n_lists`` lists, and pays with recall: a row
+whose list is not probed is not found.  The rule is restated on the CPU in tests/index_ref.py."""
+import ctypes as C
+import math
+
+import numpy as np
+
+from .gallery import Clusters, Gallery, Matches, Votes, _is_int
+from .model import Tensor
+
+#: gallery rows per workgroup of the first pass that ``parts`` is derived from: the longest list is cut into about that many
+ROWS_PER_PART = 2048
+
+
+class GalleryIndex:
+    """What ``gallery.build_index(...)`` returns: a SNAPSHOT of the gallery's first ``size`` rows as ``n_lists`` inverted
+    lists.  The index owns a copy of the bf16 rows in list order (the gallery's memory, once more), the original row of every
+    position (``ids``, ascending inside a list) and the lists' ``offsets``; ``centroids`` is the labelled ``Gallery`` of
+    ``kmeans`` and ``counts`` the rows per list.  Rows added to the gallery later are not seen until a new build: ``stale``
+    says that there are some.  ``Gallery.search``, ``classify`` and ``evaluate`` never come here."""
+
+    def __init__(self, gallery, clusters):
+        import torch
+        cen = clusters.centroids
+        n, nl = len(gallery), len(cen)
+        assignment = clusters.assignment.torch() if isinstance(clusters.assignment, Tensor) else clusters.assignment
+        self._gallery = gallery
+        self.dim, self.pitch = gallery.dim, gallery.pitch
+        self.size = n
+        self.n_lists = nl
+        self.centroids = cen
+        # plumbing, as Gallery._segment_means does it: a stable sort of the lists (rows ascend inside a list) and searchsorted
+        ordered, order = torch.sort(assignment, stable=True)
+        dev = ordered.device
+        self._offsets = torch.searchsorted(ordered, torch.arange(nl + 1, dtype=torch.int32, device=dev), out_int32=True).contiguous()
+        self._ids = order.to(torch.int32).contiguous()
+        self._rows = gallery._buf[:n].index_select(0, order).contiguous()          # bf16 (size, pitch): the rows in list order
+        self.counts = Tensor((self._offsets[1:] - self._offsets[:-1]).contiguous())
+        longest = int(self.counts.torch().max().item())                              # the build's one synchronisation
+        self.longest = longest
+        self.parts = min(max(-(-longest // ROWS_PER_PART), 1), _ffi().EMBED_LISTS_MAX_PARTS)
+        self._work = {}                                                              # (B, k, nprobe, parts) -> workspace (uint8)
+
+    # -- what the index is ---------------------------------------------------------------------------------------------------
+    @property
+    def stale(self) -> bool:
+        """whether the gallery has grown since the build: its later rows are not searched"""
+        return len(self._gallery) != self.size
+
+    def lists(self):
+        """``(ids, offsets)`` as numpy int32 arrays, (size,) and (n_lists + 1,): list ``l`` holds the original rows
+        ``ids[offsets[l] : offsets[l + 1]]``, ascending (two device -> host copies)"""
+        return self._ids.cpu().numpy(), self._offsets.cpu().numpy()
+
+    # -- arguments: every ValueError before any device work ------------------------------------------------------------------------
+    def _args(self, k, nprobe, parts=0, what="GalleryIndex.search"):
+        """every ``ValueError`` of ``search`` about ``k``, ``nprobe`` and ``parts``; returns ``parts`` resolved.  No device work."""
+        ffi = _ffi()
+        if not _is_int(k):
+            raise ValueError(f"{what}: k must be an integer, got {k!r}")
+        if not _is_int(nprobe):
+            raise ValueError(f"{what}: nprobe must be an integer, got {nprobe!r}")
+        if not _is_int(parts):
+            raise ValueError(f"{what}: parts must be an integer, got {parts!r}")
+        if k < 1 or k > ffi.EMBED_WIDE_MAX_K:
+            raise ValueError(f"{what}: k = {k}, must be in [1, TFIMM_EMBED_WIDE_MAX_K = {ffi.EMBED_WIDE_MAX_K}] (it may exceed the "
+                             f"rows probed: the slots behind them hold -1 / -inf)")
+        most = min(self.n_lists, ffi.EMBED_LISTS_MAX_PROBE)
+        if nprobe < 1 or nprobe > most:
+            raise ValueError(f"{what}: nprobe = {nprobe}, must be in [1, min(n_lists = {self.n_lists}, TFIMM_EMBED_LISTS_MAX_PROBE = "
+                             f"{ffi.EMBED_LISTS_MAX_PROBE})]")
+        try:
+            self.centroids._route(int(nprobe))                 # the probe is a search of the centroids
+        except ValueError as e:
+            raise ValueError(f"{what}: nprobe = {nprobe}: the probe is centroids.search(q, nprobe): {e}") from None
+        if parts < 0 or parts > ffi.EMBED_LISTS_MAX_PARTS:
+            raise ValueError(f"{what}: parts = {parts}, must be 0 (derived from the longest list) or in [1, {ffi.EMBED_LISTS_MAX_PARTS}]")
+        return int(parts) if parts else self.parts
+
+    def _queries(self, q, what):
+        try:
+            t = self._gallery._check_rows(q, "search")
+        except ValueError as e:
+            raise ValueError(str(e).replace("Gallery.search", what)) from None
+        if int(t.shape[0]) > _ffi().EMBED_LISTS_MAX_B:
+            raise ValueError(f"{what}: {int(t.shape[0])} queries, at most {_ffi().EMBED_LISTS_MAX_B} per call")
+        return t
+
+    # -- the search ----------------------------------------------------------------------------------------------------------------
+    def probe(self, q, nprobe: int = 8) -> Tensor:
+        """int32 ``Tensor`` (B, nprobe): ``centroids.search(q, nprobe).indices`` -- per query the ``nprobe`` best lists by
+        centroid score descending, equal scores by ascending list.  No kernel of its own."""
+        self._args(1, nprobe, 0, "GalleryIndex.probe")
+        return self.centroids.search(self._queries(q, "GalleryIndex.probe"), int(nprobe)).indices
+
+    def search(self, q, k: int = 5, nprobe: int = 8, parts: int = 0) -> Matches:
+        """``Matches(indices, scores)`` for float32 queries ``q`` (B, dim): per query the ``k`` best rows AMONG THE ``nprobe``
+        LISTS whose centroids score best -- score descending, equal scores by ascending row, rows as the gallery numbers
+        them, every score with the bits ``Gallery.search`` gives for that row.  A row in a list that is not probed is not
+        found; with ``nprobe == n_lists`` the result is ``Gallery.search``'s.  ``k <= 256`` may exceed the rows probed: the
+        slots behind them hold index -1 and score -inf.  ``1 <= nprobe <= min(n_lists, 256)``.  ``parts``: workgroups per
+        list, 0 = derived at build time from the longest list (about 2048 rows each, at most 64); the result does not depend
+        on it.  The probe's two launches and the search's two on the current stream; nothing goes to the host."""
+        import torch
+        ffi = _ffi()
+        what = "GalleryIndex.search"
+        parts = self._args(k, nprobe, parts, what)
+        t = self._gallery._upload_rows(self._queries(q, what)).contiguous()
+        B, k, nprobe = int(t.shape[0]), int(k), int(nprobe)
+        scores = torch.empty((B, k), dtype=torch.float32, device=t.device)
+        indices = torch.empty((B, k), dtype=torch.int32, device=t.device)
+        if B == 0:
+            return Matches(Tensor(indices), Tensor(scores))
+        probes = self.centroids.search(t, nprobe).indices.torch()
+        need = ffi.lib.tfimm_hip_embed_search_lists_workspace(B, self.size, self.dim, self.n_lists, nprobe, k, parts)
+        if need < 0:
+            ffi.check(int(need), "tfimm_hip_embed_search_lists_workspace")
+        work = self._work.get((B, k, nprobe, parts))
+        if work is None or work.numel() < need:
+            work = self._work[(B, k, nprobe, parts)] = torch.empty(int(need), dtype=torch.uint8, device=t.device)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(ffi.lib.tfimm_hip_embed_search_lists(t.data_ptr(), self.dim, B, self._rows.data_ptr(), self.pitch, self.size, self.dim,
+                                                       self._ids.data_ptr(), self._offsets.data_ptr(), self.n_lists, probes.data_ptr(),
+                                                       nprobe, nprobe, k, parts, scores.data_ptr(), indices.data_ptr(), work.data_ptr(),
+                                                       work.numel(), st), "tfimm_hip_embed_search_lists")
+        return Matches(Tensor(indices), Tensor(scores))
+
+    def classify(self, q, k: int = 20, nprobe: int = 8, temperature=0.07, top: int = 5, reduce: str = "sum", exclude=None) -> Votes:
+        """``gallery.vote(index.search(q, k, nprobe), ...)``: the classes of the queries from their ``k`` nearest labelled rows
+        among the probed lists; ``k <= 64``, and with ``exclude`` the search asks for ``k + 1`` rows as ``Gallery.classify``
+        does.  Slots the lists could not fill (-1) are no candidates of the vote.  Every argument is checked first."""
+        ffi = _ffi()
+        what = "GalleryIndex.classify"
+        g = self._gallery
+        g._need_labels(what)
+        inv_t, red = g._vote_args(what, temperature, top, reduce)
+        if not _is_int(k):
+            raise ValueError(f"{what}: k must be an integer, got {k!r}")
+        extra = 0 if exclude is None else 1
+        if k < 1 or k + extra > ffi.KNN_MAX_K:
+            raise ValueError(f"{what}: k = {k}{' (+ 1 for the excluded row)' if extra else ''}, must be in [1, TFIMM_KNN_MAX_K = "
+                             f"{ffi.KNN_MAX_K}{' - 1' if extra else ''}]")
+        self._args(int(k) + extra, nprobe, 0, what)
+        t = self._queries(q, what)
+        up_ex = g._exclude(exclude, int(t.shape[0]), what)
+        m = self.search(q, int(k) + extra, nprobe)
+        return g._launch_vote(m.indices.torch(), m.scores.torch(), up_ex, inv_t, red, int(top))
+
+
+def _ffi():
+    from ..engine import ffi
+    return ffi
+
+
+def _plan_index(gallery, n_lists, iters, init, seed, clusters):
+    """every ``ValueError`` of ``Gallery.build_index`` that does not belong to ``kmeans``; returns ``n_lists`` resolved (None
+    with ``clusters``).  No device work."""
+    ffi = _ffi()
+    what = "Gallery.build_index"
+    if not len(gallery):
+        raise ValueError(f"{what}: the gallery is empty")
+    if clusters is not None:
+        if not isinstance(clusters, Clusters) or not isinstance(clusters.centroids, Gallery):
+            raise ValueError(f"{what}: clusters must be the Clusters of gallery.kmeans, got {type(clusters).__name__}")
+        if n_lists is not None and n_lists != len(clusters.centroids):
+            raise ValueError(f"{what}: n_lists = {n_lists!r} with clusters of {len(clusters.centroids)} centroids: leave one out")
+        if clusters.centroids.dim != gallery.dim:
+            raise ValueError(f"{what}: clusters of dim {clusters.centroids.dim}, this gallery holds rows of {gallery.dim}")
+        if not 1 <= len(clusters.centroids) <= ffi.CLUSTER_MAX_C:
+            raise ValueError(f"{what}: clusters of {len(clusters.centroids)} centroids, must be in [1, TFIMM_CLUSTER_MAX_C = "
+                             f"{ffi.CLUSTER_MAX_C}]")
+        if tuple(clusters.assignment.shape) != (len(gallery),):
+            raise ValueError(f"{what}: clusters assign {tuple(clusters.assignment.shape)} rows, the gallery holds {len(gallery)}: "
+                             f"cluster again after an add")
+        return None
+    if n_lists is None:
+        return min(max(int(round(math.sqrt(len(gallery)))), 1), ffi.CLUSTER_MAX_C)
+    return n_lists                                             # kmeans says what is wrong with it
+
+
+def build_index(gallery, n_lists=None, iters=10, init=None, seed=0, clusters=None) -> GalleryIndex:
+    n = _plan_index(gallery, n_lists, iters, init, seed, clusters)
+    if clusters is None:
+        clusters = gallery.kmeans(n, iters, init, seed)
+    return GalleryIndex(gallery, clusters)
