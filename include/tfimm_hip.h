@@ -1214,6 +1214,42 @@ TFIMM_API int tfimm_hip_embed_search_lists(const float* q, int64_t ld_q, int B, 
                                            int nprobe, int k, int parts, float* scores, int32_t* indices, void* workspace,
                                            int64_t workspace_bytes, void* stream);
 
+/* tfimm_hip_embed_search_lists_grouped (csrc/embed_lists_grouped.hip): tfimm_hip_embed_search_lists -- the same
+ * arguments in the same order, the same rule, the same result BIT FOR BIT -- with every probed list scored once for up to 32 of
+ * the queries that name it: the 32 columns of the MFMA's B operand hold 32 different queries where the single-query kernel
+ * repeats one.  For large batches (B * nprobe well above L) the gallery bytes read fall by up to 32.
+ * A PAIR is (query b, probe slot s), P = B * nprobe of them; it is LIVE when probes[b][s] is in [0, L), no earlier slot of the
+ * query names the same list and the list is not empty (offsets clamped to [0, N]).  Six launches on `stream`:
+ *   fill    count[L] = 0 and every query's k outputs "none" (-1, -inf) -- a kernel, no memset;
+ *   rank    every live pair takes a rank among the pairs of its list (an integer atomicAdd on count);
+ *   scan    a list has ceil(count / 32) TILES: the first tile of every list and the total, one workgroup;
+ *   place   a live pair becomes member rank % 32 of tile first[l] + rank / 32; any other pair writes its k * parts workspace
+ *           entries as empty (key 0, row INT_MAX);
+ *   pass 1  grid (T_max, parts): the number of tiles exists on the device only, so the launch takes the bound
+ *           T_max = min(P / 32 + min(L, P), min(L, P) * ceil(B / 32)) (integer division; tfimm_hip_embed_search_lists_grouped_tiles)
+ *           and a workgroup whose tile is not below the total returns at once.  A workgroup gathers the tile's queries into LDS
+ *           as bf16, scores cut `part` (ceil(len / parts) rows, as in tfimm_hip_embed_search_lists) of the tile's list with the
+ *           step loop of tfimm_hip_embed_search_wide -- one buffer of (key, position) pairs per query -- and leaves every
+ *           member's k best at workspace[b][s * parts + part][k], the address and the set of the single-query kernel;
+ *   pass 2  as in tfimm_hip_embed_search_lists.
+ * The ranks differ from run to run; they move queries between tiles and lanes and no result bit depends on them.  No float
+ * atomics, no scratch memory, no allocation, nothing goes to the host, capturable; offsets are 64-bit.
+ * Limits: those of tfimm_hip_embed_search_lists, and k <= tfimm_hip_embed_search_wide_max_k(E) -- 32 buffers share LDS with the
+ * query tile: 256 up to E = 768, 254 at E = 1024, none at E = 2048 (refused with a message that names that function).
+ * workspace_bytes >= tfimm_hip_embed_search_lists_grouped_workspace(B, N, E, L, nprobe, k, parts)
+ *   = max(B, 1) * nprobe * parts * k * 8 + 4 * (L + (L + 1) + P + T_max + 32 * T_max), P and T_max taken at max(B, 1):
+ * the pair arrays of tfimm_hip_embed_search_lists, then count [L], first tile [L + 1] (the last entry: the total), rank [P], list
+ * per tile [T_max] and members [T_max][32], all int32.  TFIMM_EINVAL (negative) for arguments the search would refuse; every
+ * refusal comes before any launch with a message naming the argument.  B == 0 returns 0 and launches nothing.
+ * tfimm_hip_embed_search_lists_grouped_tiles(B, L, nprobe) returns T_max (0 for B == 0), TFIMM_EINVAL for B, L or nprobe outside
+ * the limits above. */
+TFIMM_API int64_t tfimm_hip_embed_search_lists_grouped_tiles(int B, int L, int nprobe);
+TFIMM_API int64_t tfimm_hip_embed_search_lists_grouped_workspace(int B, int N, int E, int L, int nprobe, int k, int parts);
+TFIMM_API int tfimm_hip_embed_search_lists_grouped(const float* q, int64_t ld_q, int B, const void* g, int64_t ld_g, int N, int E,
+                                                   const int32_t* ids, const int32_t* offsets, int L, const int32_t* probes,
+                                                   int64_t ld_p, int nprobe, int k, int parts, float* scores, int32_t* indices,
+                                                   void* workspace, int64_t workspace_bytes, void* stream);
+
 /* =======================================================================================
  * KNN END (csrc/knn.hip; the CPU restatement of the rule is tests/knn_ref.py): the matches of a gallery
  * search turned into classes through a label per gallery row, in one launch behind tfimm_hip_embed_search.

@@ -296,6 +296,11 @@ SYMBOLS = {
     # q, ld_q, B, g, ld_g, N, E, ids, offsets, L, probes, ld_p, nprobe, k, parts, scores, indices, workspace, workspace_bytes
     "tfimm_hip_embed_search_lists_workspace": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "tfimm_hip_embed_search_lists": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    # the same with the queries of a list grouped into MFMA tiles (csrc/embed_lists_grouped.hip): B, L, nprobe | then as above
+    "tfimm_hip_embed_search_lists_grouped_tiles": (_i64, [_i, _i, _i]),
+    "tfimm_hip_embed_search_lists_grouped_workspace": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "tfimm_hip_embed_search_lists_grouped": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64,
+                                                  _vp]),
     # the kNN end (csrc/knn.hip): indices, scores, ld, B, k, glabels, N, exclude, inv_temperature, then
     # reduce, top, classes, values, counts, total | nb_classes, labels, loss, rank, pred, prob, state, per_class, confusion
     "tfimm_hip_knn_vote": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -445,6 +450,8 @@ EMBED_COARSE_MAX_CANDIDATES = 256 # tfimm_hip_embed_search_coarse; per width: tf
 EMBED_LISTS_MAX_PROBE = 256       # tfimm_hip_embed_search_lists: lists per query
 EMBED_LISTS_MAX_PARTS = 64        # ... and cuts of a list, one workgroup each
 EMBED_LISTS_MAX_B = 65535         # ... and queries per call: one grid dimension
+EMBED_LISTS_GROUPED_TILE = 32     # tfimm_hip_embed_search_lists_grouped: queries of one list per workgroup of the first pass;
+                                  # its k obeys tfimm_hip_embed_search_wide_max_k(E) as well
 # include/tfimm_hip.h: the domain of tfimm_hip_knn_vote / tfimm_hip_knn_score (one lane per candidate and per slot of the list)
 KNN_MAX_K, KNN_MAX_TOP, KNN_SUM, KNN_MAX = EMBED_MAX_K, 64, 0, 1
 # include/tfimm_hip.h: centroids per tfimm_hip_cluster_assign; entries per run of tfimm_hip_segment_mean's summation rule

@@ -1,7 +1,9 @@
 """``GalleryIndex``: an inverted-list index over a ``Gallery`` -- the rows grouped by their best k-means centroid, and a search
 that scores only the lists a query probes (tfimm_hip_embed_search_lists, csrc/embed_lists.hip).  Every
 search path of ``Gallery`` reads the whole gallery; this one reads ``nprobe`` of ``n_lists`` lists, and pays with recall: a row
-whose list is not probed is not found.  The rule is restated on the CPU in tests/index_ref.py."""
+whose list is not probed is not found.  The rule is restated on the CPU in tests/index_ref.py.  ``search_with`` chooses the
+first pass -- one query per workgroup, or the queries of a list grouped into MFMA tiles (tfimm_hip_embed_search_lists_grouped,
+csrc/embed_lists_grouped.hip): the same bits --, and ``neighbours`` is the kNN graph of the indexed rows."""
 import ctypes as C
 import math
 
@@ -12,6 +14,9 @@ from .model import Tensor
 
 #: gallery rows per workgroup of the first pass that ``parts`` is derived from: the longest list is cut into about that many
 ROWS_PER_PART = 2048
+
+#: the first passes of ``GalleryIndex.search_with``: tfimm_hip_embed_search_lists_grouped and tfimm_hip_embed_search_lists
+_METHODS = ("grouped", "single")
 
 
 class GalleryIndex:
@@ -41,7 +46,7 @@ class GalleryIndex:
         longest = int(self.counts.torch().max().item())                              # the build's one synchronisation
         self.longest = longest
         self.parts = min(max(-(-longest // ROWS_PER_PART), 1), _ffi().EMBED_LISTS_MAX_PARTS)
-        self._work = {}                                                              # (B, k, nprobe, parts) -> workspace (uint8)
+        self._work = {}                                                              # (B, k, nprobe, parts) -> workspace (uint8); search_with: (method, B, ...)
 
     # -- what the index is ---------------------------------------------------------------------------------------------------
     @property
@@ -126,6 +131,104 @@ class GalleryIndex:
                                                        nprobe, nprobe, k, parts, scores.data_ptr(), indices.data_ptr(), work.data_ptr(),
                                                        work.numel(), st), "tfimm_hip_embed_search_lists")
         return Matches(Tensor(indices), Tensor(scores))
+
+    def _method_args(self, k, nprobe, parts, method, what):
+        """every ``ValueError`` of ``search_with`` / ``neighbours`` about ``k`` (as the search is asked for it), ``nprobe``,
+        ``parts`` and ``method``; returns ``parts`` resolved.  No device work."""
+        ffi = _ffi()
+        if method not in _METHODS:
+            raise ValueError(f"{what}: method = {method!r}, must be one of {', '.join(map(repr, _METHODS))}")
+        parts = self._args(k, nprobe, parts, what)
+        if method == "grouped":
+            wide = int(ffi.lib.tfimm_hip_embed_search_wide_max_k(self.dim))  # 32 buffers share LDS with a query tile of this width
+            if k > wide:
+                raise ValueError(f"{what}: k = {k} with method='grouped': rows of dim {self.dim} allow "
+                                 f"{'k <= ' + str(wide) if wide > 0 else 'no k'} on this path (tfimm_hip_embed_search_wide_max_k); "
+                                 f"method='single' goes up to {ffi.EMBED_WIDE_MAX_K}")
+        return parts
+
+    def _launch(self, t, probes, k, nprobe, parts, method):
+        """the search of device queries ``t`` float32 (B, dim), B >= 1, over ``probes`` int32 (B, nprobe) by ``method`` ->
+        (indices, scores) torch tensors; the launches go on the current stream"""
+        import torch
+        ffi = _ffi()
+        name = "tfimm_hip_embed_search_lists" + ("_grouped" if method == "grouped" else "")
+        B = int(t.shape[0])
+        scores = torch.empty((B, k), dtype=torch.float32, device=t.device)
+        indices = torch.empty((B, k), dtype=torch.int32, device=t.device)
+        need = getattr(ffi.lib, name + "_workspace")(B, self.size, self.dim, self.n_lists, nprobe, k, parts)
+        if need < 0:
+            ffi.check(int(need), name + "_workspace")
+        work = self._work.get((method, B, k, nprobe, parts))
+        if work is None or work.numel() < need:
+            work = self._work[(method, B, k, nprobe, parts)] = torch.empty(int(need), dtype=torch.uint8, device=t.device)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(getattr(ffi.lib, name)(t.data_ptr(), int(t.stride(0)), B, self._rows.data_ptr(), self.pitch, self.size, self.dim,
+                                         self._ids.data_ptr(), self._offsets.data_ptr(), self.n_lists, probes.data_ptr(), nprobe, nprobe,
+                                         k, parts, scores.data_ptr(), indices.data_ptr(), work.data_ptr(), work.numel(), st), name)
+        return indices, scores
+
+    def search_with(self, q, k: int = 5, nprobe: int = 8, parts: int = 0, method: str = "grouped") -> Matches:
+        """``search`` by a chosen first pass: the same ``Matches``, bit for bit.  ``method="single"`` is ``search``'s
+        (tfimm_hip_embed_search_lists: one workgroup per query, probed list and part, so every query reads its lists on its
+        own); ``"grouped"`` scores every probed list once for up to 32 of the queries that name it
+        (tfimm_hip_embed_search_lists_grouped): fewer gallery bytes when the batch names a list many times
+        (``B * nprobe`` well above ``n_lists``), more work per query when it does not.  ``"grouped"`` keeps 32 buffers in LDS:
+        ``k <= tfimm_hip_embed_search_wide_max_k(dim)`` -- 256 up to dim 768, 254 at 1024, nothing at 2048.  There is no
+        ``"auto"``: DESIGN.md 3.29 has the measurements one would be placed by.  The workspace is cached per
+        ``(method, B, k, nprobe, parts)``."""
+        import torch
+        what = "GalleryIndex.search_with"
+        parts = self._method_args(k, nprobe, parts, method, what)
+        t = self._gallery._upload_rows(self._queries(q, what)).contiguous()
+        B, k, nprobe = int(t.shape[0]), int(k), int(nprobe)
+        if B == 0:
+            return Matches(Tensor(torch.empty((0, k), dtype=torch.int32, device=t.device)),
+                           Tensor(torch.empty((0, k), dtype=torch.float32, device=t.device)))
+        probes = self.centroids.search(t, nprobe).indices.torch()
+        indices, scores = self._launch(t, probes, k, nprobe, parts, method)
+        return Matches(Tensor(indices), Tensor(scores))
+
+    def neighbours(self, k: int = 20, nprobe: int = 8, batch: int = 8192, method: str = "grouped") -> Matches:
+        """The kNN graph of the indexed rows: ``Matches`` of shape (size, k), row ``i`` the ``k`` nearest OTHER indexed rows of
+        original row ``i`` among the lists it probes, in ``search``'s order (-1 / -inf behind short results).  The rows are
+        their own queries (exact from bf16) and go in LIST order, ``batch`` at a time: a batch then names few lists and fills
+        its tiles.  Each batch is searched for ``k + 1`` -- which obeys the limits of ``search_with`` --; of every result row
+        the entry that is the row itself is dropped, or the LAST entry where the row is absent (more than ``k`` equal rows
+        with lower numbers come first).  ``torch`` ops on the device between the launches; nothing goes to the host.
+        ``1 <= batch <= 65535``."""
+        import torch
+        what = "GalleryIndex.neighbours"
+        if not _is_int(k):
+            raise ValueError(f"{what}: k must be an integer, got {k!r}")
+        if not _is_int(batch):
+            raise ValueError(f"{what}: batch must be an integer, got {batch!r}")
+        if batch < 1 or batch > _ffi().EMBED_LISTS_MAX_B:
+            raise ValueError(f"{what}: batch = {batch}, must be in [1, {_ffi().EMBED_LISTS_MAX_B}]")
+        if k < 1:
+            raise ValueError(f"{what}: k = {k}, must be at least 1")
+        try:
+            parts = self._method_args(int(k) + 1, nprobe, 0, method, what)
+        except ValueError as e:
+            raise ValueError(str(e).replace(f"k = {int(k) + 1}", f"k = {k} (+ 1 for the row itself)", 1)) from None
+        k, nprobe, batch = int(k), int(nprobe), int(batch)
+        dev = self._rows.device
+        out_idx = torch.empty((self.size, k), dtype=torch.int32, device=dev)
+        out_sc = torch.empty((self.size, k), dtype=torch.float32, device=dev)
+        cols = torch.arange(k, device=dev)[None, :]
+        for p0 in range(0, self.size, batch):
+            p1 = min(p0 + batch, self.size)
+            t = self._rows[p0:p1, :self.dim].float().contiguous()
+            own = self._ids[p0:p1]
+            probes = self.centroids.search(t, nprobe).indices.torch()
+            indices, scores = self._launch(t, probes, k + 1, nprobe, parts, method)
+            is_self = indices == own[:, None]                               # at most one per row: a row is never returned twice
+            at = torch.where(is_self.any(1), is_self.int().argmax(1), k)   # the column dropped: the row itself, or the last
+            take = cols + (cols >= at[:, None]).long()                      # a gather of fixed shape: no synchronisation
+            rows = own.long()
+            out_idx[rows] = indices.gather(1, take)
+            out_sc[rows] = scores.gather(1, take)
+        return Matches(Tensor(out_idx), Tensor(out_sc))
 
     def classify(self, q, k: int = 20, nprobe: int = 8, temperature=0.07, top: int = 5, reduce: str = "sum", exclude=None) -> Votes:
         """``gallery.vote(index.search(q, k, nprobe), ...)``: the classes of the queries from their ``k`` nearest labelled rows
