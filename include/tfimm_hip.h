@@ -530,13 +530,15 @@ TFIMM_API int tfimm_hip_layernorm(const void* x, void* y, const float* gamma, co
 typedef struct tfimm_attn_desc {
   const void* qkv;        /* bf16 [rows][3*heads*hd] */
   void* out;              /* bf16 [rows][heads*hd]   */
-  const float* rel_bias;  /* fp32 [heads][n][n] or NULL */
+  const float* rel_bias;  /* fp32 [heads][n][n] or NULL (NULL: no bias, and then no bias_log2 either) */
   int32_t batch;          /* images */
   int32_t n_tokens;       /* tokens per image (global) / res_h*res_w (window) */
   int32_t heads, hd;
   float scale;
   int32_t window, shift, res_h, res_w;
-  const float* bias_log2; /* optional (window > 0): rel_bias with the shift mask already added and everything
+  const float* bias_log2; /* optional (window > 0), accompanies rel_bias and never replaces it (some kernels read the
+                             tiles, others rel_bias: tiles with rel_bias == NULL return TFIMM_EINVAL):
+                             rel_bias with the shift mask already added and everything
                              multiplied by log2(e), one tile per window kind:
                              [kinds][heads][n][ceil64(n)], kinds = 1 (shift == 0) or 4 (shift > 0; kind =
                              2 * (last window row) + (last window column) -- the only four distinct

@@ -16,6 +16,7 @@
 //     rows are loaded and stored; the -100 shift mask is recomputed from region ids.
 #include "common.h"
 
+#include <cstdio>
 #include <cstdlib>
 
 namespace {
@@ -1173,18 +1174,47 @@ static int launch_attn_resident(const AttnArgs& a, int64_t nseq, hipStream_t st)
   return 0;
 }
 
-// waves x query tiles per wave that cover ceil(n / 16) tiles: <= 4 -> 4x1, <= 8 -> 8x1, <= 16 -> 8x2
-template <int HD, bool SWIN>
-static int launch_attn_resident_any(const AttnArgs& a, int64_t nseq, hipStream_t st) {
-  const int tiles = (a.n + 15) / 16;
-  if (tiles <= 4) return launch_attn_resident<HD, SWIN, 4, 1>(a, nseq, st);
-  if (tiles <= 8) return launch_attn_resident<HD, SWIN, 8, 1>(a, nseq, st);
-  return launch_attn_resident<HD, SWIN, 8, 2>(a, nseq, st);
+// ---- the route: which kernel instantiation a validated call runs ----------------------------------------------------------
+// tfimm_hip_attention = attn_validate (descriptor -> AttnArgs, or a refusal) + attn_route (a pure host function of the
+// arguments and the switches: no device, no HIP call) + attn_launch (grids, LDS sizes, function attributes).
+enum AttnKind { ATTN_GENERIC, ATTN_RESIDENT, ATTN_STREAM, ATTN_WINDOW_PERSIST, ATTN_WINDOW_V1 };
+
+struct AttnRoute {
+  AttnKind kind;
+  int hd;       // the HD template argument (32, 64, 96, 128)
+  bool swin;    // generic / resident: the SWIN template argument
+  int nw, tq;   // resident: waves x 16-query tiles per wave
+  int hpw;      // window_persist: heads per workgroup
+};
+
+// the environment switches, read once per process at the first call of the entry point or of the route export
+struct AttnSwitches {
+  bool resident;    // TFIMM_ATTN_NO_RESIDENT=1 clears it: everything on attn_kernel
+  bool stream;      // TFIMM_ATTN_NO_STREAM clears it
+  bool window;      // TFIMM_ATTN_NO_WINDOW clears it
+  bool win_v1;      // TFIMM_ATTN_WIN_V1: the one-window-per-workgroup kernel instead of the chunked one (A/B)
+  int64_t win_wgs;  // TFIMM_ATTN_WIN_WGS: workgroups the window kernels aim for (4096 = 16 per CU)
+  int dbg;          // TFIMM_ATTN_DBG (profiling only)
+  int xcd;          // TFIMM_ATTN_XCD=0: no XCD-contiguous item ranges in the resident kernel
+};
+
+const AttnSwitches& attn_switches() {
+  static const AttnSwitches sw = [] {
+    AttnSwitches s;
+    const char* e = getenv("TFIMM_ATTN_NO_RESIDENT");
+    s.resident = !(e && e[0] == '1');
+    s.stream = getenv("TFIMM_ATTN_NO_STREAM") == nullptr;
+    s.window = getenv("TFIMM_ATTN_NO_WINDOW") == nullptr;
+    s.win_v1 = getenv("TFIMM_ATTN_WIN_V1") != nullptr;
+    s.win_wgs = getenv("TFIMM_ATTN_WIN_WGS") ? atoi(getenv("TFIMM_ATTN_WIN_WGS")) : 4096;
+    s.dbg = getenv("TFIMM_ATTN_DBG") ? atoi(getenv("TFIMM_ATTN_DBG")) : 0;
+    s.xcd = getenv("TFIMM_ATTN_XCD") ? atoi(getenv("TFIMM_ATTN_XCD")) : 1;
+    return s;
+  }();
+  return sw;
 }
 
-}  // namespace
-
-extern "C" int tfimm_hip_attention(const tfimm_attn_desc* dp, void* stream) {
+int attn_validate(const tfimm_attn_desc* dp, const AttnSwitches& sw, AttnArgs* ap, int64_t* nseq) {
   if (!dp) TFIMM_FAIL(TFIMM_EINVAL, "attention: null descriptor");
   const tfimm_attn_desc& d = *dp;
   if (!d.qkv || !d.out) TFIMM_FAIL(TFIMM_EINVAL, "attention: null pointer");
@@ -1192,17 +1222,18 @@ extern "C" int tfimm_hip_attention(const tfimm_attn_desc* dp, void* stream) {
     TFIMM_FAIL(TFIMM_EINVAL, "attention: bad shape");
   if (d.hd > 128) TFIMM_FAIL(TFIMM_EUNSUP, "attention: head dim %d > 128 not built", d.hd);
   if (d.hd > 64 && d.window > 0) TFIMM_FAIL(TFIMM_EUNSUP, "attention: windows with head dim %d > 64 not built", d.hd);
-  AttnArgs a;
+  // the generic kernel takes its bias from rel_bias, the resident and window kernels from the tiles when there are any:
+  // tiles alone would lose the bias on some routes and keep it on others
+  if (d.window > 0 && d.bias_log2 && !d.rel_bias)
+    TFIMM_FAIL(TFIMM_EINVAL, "attention: bias_log2 tiles without rel_bias");
+  AttnArgs& a = *ap;
   a.qkv = (const bf16_t*)d.qkv; a.out = (bf16_t*)d.out; a.rel_bias = d.rel_bias;
   a.bias_log2 = d.window > 0 ? d.bias_log2 : nullptr;
   a.batch = d.batch; a.n_tokens = d.n_tokens; a.heads = d.heads; a.hd = d.hd; a.scale = d.scale;
   a.window = d.window; a.shift = d.shift; a.res_h = d.res_h; a.res_w = d.res_w;
   a.dmodel = d.heads * d.hd; a.ld = 3 * a.dmodel;
-  static const int attn_dbg = getenv("TFIMM_ATTN_DBG") ? atoi(getenv("TFIMM_ATTN_DBG")) : 0;
-  a.dbg = attn_dbg;
-  static const int attn_xcd = getenv("TFIMM_ATTN_XCD") ? atoi(getenv("TFIMM_ATTN_XCD")) : 1;
-  a.xcd_map = attn_xcd;
-  int64_t nseq;
+  a.dbg = sw.dbg;
+  a.xcd_map = sw.xcd;
   if (d.window > 0) {
     if (d.res_h <= 0 || d.res_w <= 0 || d.res_h % d.window || d.res_w % d.window ||
         d.res_h * d.res_w != d.n_tokens || d.shift < 0 || d.shift >= d.window)
@@ -1210,93 +1241,151 @@ extern "C" int tfimm_hip_attention(const tfimm_attn_desc* dp, void* stream) {
     a.n = d.window * d.window;
     a.nwx = d.res_w / d.window;
     a.nw = a.nwx * (d.res_h / d.window);
-    nseq = (int64_t)d.batch * a.nw;
+    *nseq = (int64_t)d.batch * a.nw;
   } else {
     a.n = d.n_tokens; a.nwx = 1; a.nw = 1;
-    nseq = d.batch;
+    *nseq = d.batch;
   }
   a.qchunks = (a.n + 63) / 64;
   a.vec = ((d.hd & 7) == 0) && (((uintptr_t)d.qkv & 15) == 0) && (((uintptr_t)d.out & 7) == 0);
-  const int64_t nblocks = nseq * d.heads * a.qchunks;
-  if (nblocks > 0x7fffffffLL) TFIMM_FAIL(TFIMM_EINVAL, "attention: grid too large");
-  const dim3 grid((unsigned)nblocks), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (d.hd > 64) {
+  // one workgroup per (sequence, head, 64-query chunk) is the largest grid of any route
+  if (*nseq * d.heads * a.qchunks > 0x7fffffffLL) TFIMM_FAIL(TFIMM_EINVAL, "attention: grid too large");
+  return 0;
+}
+
+AttnRoute attn_route(const AttnArgs& a, int64_t nseq, const AttnSwitches& sw) {
+  const bool swin = a.window > 0;
+  AttnRoute r{ATTN_GENERIC, 0, swin, 0, 0, 0};
+  if (a.hd > 64) {
     // head dims 65..128 (vit_huge_patch14: 80): the streaming kernel with three / four MFMA k-steps over the head dimension
     // and six / eight output tiles per wave; the columns beyond hd are zero in K, Q and V
-    if (d.hd <= 96) TFIMM_LAUNCH((attn_kernel<96, false>), grid, block, 0, st, a);
-    else TFIMM_LAUNCH((attn_kernel<128, false>), grid, block, 0, st, a);
-    return 0;
+    r.hd = a.hd <= 96 ? 96 : 128;
+    return r;
   }
-  {
-    // K + V^T (+ Swin bias tile) of one (sequence, head) resident in LDS (<= 80 KiB: two workgroups per CU)
-    const bool tl = d.window > 0 && d.bias_log2 != nullptr;
-    const size_t lds = d.hd <= 32 ? attn_resident_lds<32>(a.n, d.window > 0, tl) : attn_resident_lds<64>(a.n, d.window > 0, tl);
-    static int use_resident = -1;
-    if (use_resident < 0) {
-      const char* e = getenv("TFIMM_ATTN_NO_RESIDENT");
-      use_resident = (e && e[0] == '1') ? 0 : 1;
-    }
-    // global attention at head dim 64 with 9..16 query tiles (n = 129..256: ViT / DeiT / CaiT at 224) and enough items
-    // to keep every CU's workgroup busy for several rounds: the persistent kernel (measured 5-9 % faster on ViT-B;
-    // no gain at head dim 32 or with few heads, which stay on the kernel below)
-    static const bool no_stream = getenv("TFIMM_ATTN_NO_STREAM") != nullptr;
-    if (use_resident && !no_stream && d.window == 0 && a.vec && a.n > 128 && a.n <= 256 && d.hd == 64 &&
-        nseq * d.heads >= 2048 && nseq * d.heads <= 0x7fffffffLL)
+  r.hd = a.hd <= 32 ? 32 : 64;
+  if (!sw.resident) return r;
+  // global attention at head dim 64 with 9..16 query tiles (n = 129..256: ViT / DeiT / CaiT at 224) and enough items
+  // to keep every CU's workgroup busy for several rounds: the persistent kernel (measured 5-9 % faster on ViT-B;
+  // no gain at head dim 32 or with few heads, which stay on the resident kernel)
+  if (sw.stream && !swin && a.vec && a.n > 128 && a.n <= 256 && a.hd == 64 && nseq * a.heads >= 2048) {
+    r.kind = ATTN_STREAM;
+    return r;
+  }
+  // Swin windows (head dim 32, <= 64 tokens, pre-combined bias tiles): a workgroup owns a window and a range of its heads.
+  // (round 6) bias tiles out of the window loop: a workgroup owns HPW heads and a chunk of windows of one mask kind
+  // (attn_window_persist_kernel); TFIMM_ATTN_WIN_V1=1 keeps the one-window-per-workgroup kernel (A/B)
+  const bool tl = a.bias_log2 != nullptr;
+  if (sw.window && tl && a.vec && a.hd == 32 && a.n <= 64) {
+    r.kind = sw.win_v1 ? ATTN_WINDOW_V1 : ATTN_WINDOW_PERSIST;
+    r.hpw = sw.win_v1 ? 0 : (a.heads % 2 == 0 ? 2 : 1);
+    return r;
+  }
+  // K + V^T (+ Swin bias tile) of one (sequence, head) resident in LDS (<= 80 KiB: two workgroups per CU)
+  const size_t lds = r.hd == 32 ? attn_resident_lds<32>(a.n, swin, tl) : attn_resident_lds<64>(a.n, swin, tl);
+  if (lds <= 80 * 1024 && a.n <= 256) {
+    // waves x query tiles per wave that cover ceil(n / 16) tiles: <= 4 -> 4x1, <= 8 -> 8x1, <= 16 -> 8x2
+    const int tiles = (a.n + 15) / 16;
+    r.kind = ATTN_RESIDENT;
+    r.nw = tiles <= 4 ? 4 : 8;
+    r.tq = tiles <= 8 ? 1 : 2;
+  }
+  return r;
+}
+
+// the route's stable name: generic<96,global>, resident<64,swin,8x2>, stream<64>, window_persist<32,hpw2>, window_v1<32>
+void attn_route_name(const AttnRoute& r, char* name, size_t len) {
+  const char* kind = r.swin ? "swin" : "global";
+  switch (r.kind) {
+    case ATTN_GENERIC: snprintf(name, len, "generic<%d,%s>", r.hd, kind); break;
+    case ATTN_RESIDENT: snprintf(name, len, "resident<%d,%s,%dx%d>", r.hd, kind, r.nw, r.tq); break;
+    case ATTN_STREAM: snprintf(name, len, "stream<%d>", r.hd); break;
+    case ATTN_WINDOW_PERSIST: snprintf(name, len, "window_persist<%d,hpw%d>", r.hd, r.hpw); break;
+    case ATTN_WINDOW_V1: snprintf(name, len, "window_v1<%d>", r.hd); break;
+  }
+}
+
+template <int HD, bool SWIN>
+int launch_attn_resident_any(const AttnRoute& r, const AttnArgs& a, int64_t nseq, hipStream_t st) {
+  if (r.nw == 4) return launch_attn_resident<HD, SWIN, 4, 1>(a, nseq, st);
+  if (r.tq == 1) return launch_attn_resident<HD, SWIN, 8, 1>(a, nseq, st);
+  return launch_attn_resident<HD, SWIN, 8, 2>(a, nseq, st);
+}
+
+int attn_launch(const AttnRoute& r, const AttnArgs& a, int64_t nseq, const AttnSwitches& sw, hipStream_t st) {
+  switch (r.kind) {
+    case ATTN_STREAM:
       return launch_attn_stream<64, 16, 1>(a, nseq, st);
-    // Swin windows (head dim 32, <= 64 tokens, pre-combined bias tiles): a workgroup owns a window and a range of its heads
-    static const bool no_window = getenv("TFIMM_ATTN_NO_WINDOW") != nullptr;
-    if (use_resident && !no_window && tl && a.vec && d.hd == 32 && a.n <= 64 && nseq * d.heads <= 0x7fffffffLL) {
+    case ATTN_WINDOW_PERSIST: {
+      const int hsplit = a.heads / r.hpw;
+      const int nwy = a.nw / a.nwx;
+      WinSched ws;
+      if (a.shift > 0) {
+        ws.cnt[0] = (nwy - 1) * (a.nwx - 1); ws.cnt[1] = nwy - 1; ws.cnt[2] = a.nwx - 1; ws.cnt[3] = 1;
+      } else {
+        ws.cnt[0] = a.nw; ws.cnt[1] = ws.cnt[2] = ws.cnt[3] = 0;
+      }
+      // windows per chunk: as many as leave ~4096 workgroups (16 per CU), at most 16
+      int64_t wpb = nseq * hsplit / sw.win_wgs;
+      wpb = wpb < 1 ? 1 : (wpb > 16 ? 16 : wpb);
+      ws.wpb = (int)wpb;
+      int64_t total = 0;
+      for (int k = 0; k < 4; ++k) {
+        ws.first[k] = (int)total;
+        total += ((int64_t)a.batch * ws.cnt[k] + wpb - 1) / wpb;
+      }
+      ws.first[4] = (int)total;
+      // the four counts add up to the windows of an image and ceil(x / wpb) <= x, so total <= nseq and the grid is within
+      // the nseq * heads * qchunks that attn_validate bounds by 2^31 - 1
+      const dim3 grid((unsigned)(total * hsplit));
+      if (r.hpw == 2) TFIMM_LAUNCH((attn_window_persist_kernel<32, 2>), grid, dim3(256), 0, st, a, hsplit, ws);
+      else TFIMM_LAUNCH((attn_window_persist_kernel<32, 1>), grid, dim3(256), 0, st, a, hsplit, ws);
+      return 0;
+    }
+    case ATTN_WINDOW_V1: {
       // heads per workgroup: split a window's heads over workgroups until there are ~16 workgroups per CU (measured on Swin-B:
       // 2.00 ms of attention at a 1024-workgroup threshold, 1.93 at 4096)
-      // (round 6) bias tiles out of the window loop: a workgroup owns HPW heads and a chunk of windows of one mask kind
-      // (attn_window_persist_kernel); TFIMM_ATTN_WIN_V1=1 keeps the one-window-per-workgroup kernel (A/B)
-      static const bool win_v1 = getenv("TFIMM_ATTN_WIN_V1") != nullptr;
-      if (!win_v1) {
-        const int hpw = (d.heads % 2 == 0) ? 2 : 1;
-        const int hsplit2 = d.heads / hpw;
-        const int nwy = a.nw / a.nwx;
-        WinSched ws;
-        if (d.shift > 0) {
-          ws.cnt[0] = (nwy - 1) * (a.nwx - 1); ws.cnt[1] = nwy - 1; ws.cnt[2] = a.nwx - 1; ws.cnt[3] = 1;
-        } else {
-          ws.cnt[0] = a.nw; ws.cnt[1] = ws.cnt[2] = ws.cnt[3] = 0;
-        }
-        // windows per chunk: as many as leave ~4096 workgroups (16 per CU), at most 16
-        static const int64_t win_wgs2 = getenv("TFIMM_ATTN_WIN_WGS") ? atoi(getenv("TFIMM_ATTN_WIN_WGS")) : 4096;
-        int64_t wpb = nseq * hsplit2 / win_wgs2;
-        wpb = wpb < 1 ? 1 : (wpb > 16 ? 16 : wpb);
-        ws.wpb = (int)wpb;
-        int64_t total = 0;
-        for (int k = 0; k < 4; ++k) {
-          ws.first[k] = (int)total;
-          total += ((int64_t)d.batch * ws.cnt[k] + wpb - 1) / wpb;
-        }
-        ws.first[4] = (int)total;
-        if (total * hsplit2 <= 0x7fffffffLL) {
-          if (hpw == 2) TFIMM_LAUNCH((attn_window_persist_kernel<32, 2>), dim3((unsigned)(total * hsplit2)), dim3(256), 0, st, a, hsplit2, ws);
-          else TFIMM_LAUNCH((attn_window_persist_kernel<32, 1>), dim3((unsigned)(total * hsplit2)), dim3(256), 0, st, a, hsplit2, ws);
-          return 0;
-        }
-      }
       int hsplit = 1;
-      static const int64_t win_wgs = getenv("TFIMM_ATTN_WIN_WGS") ? atoi(getenv("TFIMM_ATTN_WIN_WGS")) : 4096;
-      while (hsplit < d.heads && nseq * hsplit < win_wgs && d.heads % (hsplit * 2) == 0) hsplit *= 2;
+      while (hsplit < a.heads && nseq * hsplit < sw.win_wgs && a.heads % (hsplit * 2) == 0) hsplit *= 2;
       TFIMM_LAUNCH((attn_window_kernel<32>), dim3((unsigned)(nseq * hsplit)), dim3(256), 0, st, a, hsplit);
       return 0;
     }
-    if (use_resident && lds <= 80 * 1024 && a.n <= 256 && nseq * d.heads <= 0x7fffffffLL) {
-      if (d.window > 0)
-        return d.hd <= 32 ? launch_attn_resident_any<32, true>(a, nseq, st) : launch_attn_resident_any<64, true>(a, nseq, st);
-      return d.hd <= 32 ? launch_attn_resident_any<32, false>(a, nseq, st) : launch_attn_resident_any<64, false>(a, nseq, st);
+    case ATTN_RESIDENT:
+      if (r.swin)
+        return r.hd == 32 ? launch_attn_resident_any<32, true>(r, a, nseq, st) : launch_attn_resident_any<64, true>(r, a, nseq, st);
+      return r.hd == 32 ? launch_attn_resident_any<32, false>(r, a, nseq, st) : launch_attn_resident_any<64, false>(r, a, nseq, st);
+    case ATTN_GENERIC: {
+      const dim3 grid((unsigned)(nseq * a.heads * a.qchunks)), block(256);
+      if (r.hd == 128) TFIMM_LAUNCH((attn_kernel<128, false>), grid, block, 0, st, a);
+      else if (r.hd == 96) TFIMM_LAUNCH((attn_kernel<96, false>), grid, block, 0, st, a);
+      else if (r.swin && r.hd == 32) TFIMM_LAUNCH((attn_kernel<32, true>), grid, block, 0, st, a);
+      else if (r.swin) TFIMM_LAUNCH((attn_kernel<64, true>), grid, block, 0, st, a);
+      else if (r.hd == 32) TFIMM_LAUNCH((attn_kernel<32, false>), grid, block, 0, st, a);
+      else TFIMM_LAUNCH((attn_kernel<64, false>), grid, block, 0, st, a);
+      return 0;
     }
   }
-  if (d.window > 0) {
-    if (d.hd <= 32) TFIMM_LAUNCH((attn_kernel<32, true>), grid, block, 0, st, a);
-    else TFIMM_LAUNCH((attn_kernel<64, true>), grid, block, 0, st, a);
-  } else {
-    if (d.hd <= 32) TFIMM_LAUNCH((attn_kernel<32, false>), grid, block, 0, st, a);
-    else TFIMM_LAUNCH((attn_kernel<64, false>), grid, block, 0, st, a);
-  }
+  TFIMM_FAIL(TFIMM_EINVAL, "attention: no route");
+}
+
+}  // namespace
+
+extern "C" int tfimm_hip_attention(const tfimm_attn_desc* dp, void* stream) {
+  const AttnSwitches& sw = attn_switches();
+  AttnArgs a;
+  int64_t nseq;
+  if (int rc = attn_validate(dp, sw, &a, &nseq)) return rc;
+  return attn_launch(attn_route(a, nseq, sw), a, nseq, sw, (hipStream_t)stream);
+}
+
+// Debug export (default visibility, not in the public header): the name of the route tfimm_hip_attention would take for this
+// descriptor -- the same attn_validate + attn_route, the same switches -- or the refusal code.  Launches nothing and touches
+// no device; the pointers only need the alignment of the real ones.
+extern "C" __attribute__((visibility("default"))) int tfimm_hip_dbg_attention_route(const tfimm_attn_desc* dp, char* name, size_t len) {
+  if (!name || len == 0) TFIMM_FAIL(TFIMM_EINVAL, "attention route: no name buffer");
+  const AttnSwitches& sw = attn_switches();
+  AttnArgs a;
+  int64_t nseq;
+  if (int rc = attn_validate(dp, sw, &a, &nseq)) return rc;
+  attn_route_name(attn_route(a, nseq, sw), name, len);
   return 0;
 }

@@ -204,15 +204,34 @@ def layernorm(x, gamma, beta, eps, rows=None, d=None, xs=None, ys=None, out=None
     return out
 
 
-def attention(qkv, batch, n_tokens, heads, hd, scale, window=0, shift=0, res=(0, 0), rel_bias=None, bias_log2=None):
-    out = torch.empty(batch * n_tokens, heads * hd, dtype=torch.bfloat16, device=DEV)
+def attn_desc(qkv, out, batch, n_tokens, heads, hd, scale, window=0, shift=0, res=(0, 0), rel_bias=None, bias_log2=None):
+    """tfimm_attn_desc from raw addresses (integers or None)"""
     d = ffi.AttnDesc()
-    d.qkv, d.out, d.rel_bias = ptr(qkv), ptr(out), ptr(rel_bias)
-    d.bias_log2 = ptr(bias_log2)
+    d.qkv, d.out, d.rel_bias, d.bias_log2 = qkv, out, rel_bias, bias_log2
     d.batch, d.n_tokens, d.heads, d.hd, d.scale = batch, n_tokens, heads, hd, float(scale)
     d.window, d.shift, d.res_h, d.res_w = window, shift, res[0], res[1]
+    return d
+
+
+def attention(qkv, batch, n_tokens, heads, hd, scale, window=0, shift=0, res=(0, 0), rel_bias=None, bias_log2=None, out=None):
+    """``out``: the caller's output tensor (a view at some byte offset of a larger allocation) instead of a fresh one"""
+    if out is None:
+        out = torch.empty(batch * n_tokens, heads * hd, dtype=torch.bfloat16, device=DEV)
+    d = attn_desc(ptr(qkv), ptr(out), batch, n_tokens, heads, hd, scale, window, shift, res, ptr(rel_bias), ptr(bias_log2))
     ffi.check(lib.tfimm_hip_attention(C.byref(d), stream()), "attention")
     return out
+
+
+lib.tfimm_hip_dbg_attention_route.restype = C.c_int
+lib.tfimm_hip_dbg_attention_route.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+
+
+def attention_route(d):
+    """(0, name of the kernel instantiation tfimm_hip_attention would launch for descriptor ``d``) or (refusal code, message):
+    the library's debug export, which validates and routes and touches no device (``d`` may be None: the null descriptor)"""
+    name = C.create_string_buffer(64)
+    rc = lib.tfimm_hip_dbg_attention_route(None if d is None else C.byref(d), name, len(name))
+    return rc, (name.value if rc == 0 else lib.tfimm_hip_last_error()).decode()
 
 
 def talking_heads_attention(qkv, batch, n_tokens, heads, hd, scale, wl, bl, ww, bw, use_dev=True):

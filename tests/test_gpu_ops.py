@@ -125,13 +125,13 @@ def test_recorded_zeroing_writes_its_value_on_every_replay(nbytes, offset):
 def test_swin_one_window_per_workgroup_kernel_holds_the_tight_bars():
     """attn_window_kernel, the one-window-per-workgroup Swin kernel that TFIMM_ATTN_WIN_V1=1 selects instead of the chunked
     attn_window_persist_kernel (read once per process, hence the subprocess): the tight_swin_tiles_* cases of head dim 32 and
-    7 x 7 windows, same references, same bars."""
+    7 x 7 and 8 x 8 windows, same references, same bars."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    names = sorted(n for n in hip_checks.CASES if n.startswith("tight_swin_tiles_w7"))
-    assert len(names) >= 8
+    names = sorted(n for n in hip_checks.CASES if n.startswith(("tight_swin_tiles_w7", "tight_swin_tiles_w8")))   # w8: full 64-token windows
+    assert len(names) >= 10
     code = ("import sys; sys.path[:0] = [%r, %r, %r]; import hip_checks\n"
             "for n in %r:\n"
             "    e, t = hip_checks.run_case(n); print(n, e, t); assert e <= t, (n, e, t)\n"
@@ -139,3 +139,65 @@ def test_swin_one_window_per_workgroup_kernel_holds_the_tight_bars():
     env = dict(os.environ, TFIMM_ATTN_WIN_V1="1")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+
+
+# ---- the other switches of the attention dispatcher: the fall-backs behind them are what the lds > 80 KiB, n > 256 and
+# unaligned-pointer conditions take in production.  One child per environment (each switch is read once per process), run
+# one after the other; a child checks each row's route under its switch (hip_checks.ATTN_SWITCHES), then runs it against the
+# same reference under the same bars, and stops at its first failure.
+_TIGHT_ATTN = sorted(n for n in hip_checks.ATTN_ROWS if n.startswith("tight_"))
+_WINDOW_KERNEL_ROWS = [n for n in _TIGHT_ATTN if n.startswith(("tight_swin_tiles_w7", "tight_swin_tiles_w8"))]
+_B65 = ["tight_swin_tiles_w7_shift3_56x56_b65_wpb2", "tight_swin_tiles_w7_noshift_56x56_b65_wpb2"]
+
+
+def _attention_child(setting, names):
+    import os
+    import subprocess
+    import sys
+    assert names and all(n in hip_checks.CASES for n in names)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]; import hip_checks\n"
+            "hip_checks.attn_rows_under(%r, %r)\n"
+            % (root, os.path.join(root, "tensorflow-image-models_amd"), os.path.join(root, "tests"), setting, names))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("TFIMM_ATTN_")}
+    key, value = setting.split("=")
+    env[key] = value
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    assert len([ln for ln in r.stdout.splitlines() if ln.startswith("tight_")]) == len(names)
+
+
+def test_attention_without_resident_kernels_holds_the_tight_bars():
+    """TFIMM_ATTN_NO_RESIDENT=1: every tight attention row on attn_kernel, all six instantiations (the two 65-image window
+    cases and the 171-image stream case left out: the same kernels as their small twins, many times the reference)"""
+    names = [n for n in _TIGHT_ATTN if n not in _B65 + ["tight_attn_stream_197_multiround"]]
+    routes = {hip_checks.ATTN_SWITCHES["TFIMM_ATTN_NO_RESIDENT=1"](None, hip_checks.ATTN_ROWS[n]) for n in names}
+    assert len(routes) == 6, routes
+    _attention_child("TFIMM_ATTN_NO_RESIDENT=1", names)
+
+
+def test_attention_without_stream_kernel_holds_the_tight_bars():
+    """TFIMM_ATTN_NO_STREAM=1: the stream shapes on attn_resident_kernel<64, false, 8, 2> (the kernel they had before)"""
+    names = [n for n in _TIGHT_ATTN if hip_checks.ATTN_ROWS[n]["route"] == "stream<64>"]
+    assert names == ["tight_attn_stream_129_spike", "tight_attn_stream_197_multiround"]
+    _attention_child("TFIMM_ATTN_NO_STREAM=1", names)
+
+
+def test_swin_without_window_kernels_holds_the_tight_bars():
+    """TFIMM_ATTN_NO_WINDOW=1: the window-kernel shapes on attn_resident_kernel<32, true, 4, 1> with bias tiles"""
+    assert sum(hip_checks.ATTN_ROWS[n]["route"].startswith("window_persist") for n in _WINDOW_KERNEL_ROWS) >= 11
+    _attention_child("TFIMM_ATTN_NO_WINDOW=1", _WINDOW_KERNEL_ROWS)
+
+
+def test_attention_resident_kernels_without_xcd_ranges_hold_the_tight_bars():
+    """TFIMM_ATTN_XCD=0: attn_resident_kernel with workgroup = item instead of XCD-contiguous item ranges, all twelve instantiations"""
+    names = [n for n in _TIGHT_ATTN if hip_checks.ATTN_ROWS[n]["route"].startswith("resident<")]
+    assert len({hip_checks.ATTN_ROWS[n]["route"] for n in names}) == 12
+    _attention_child("TFIMM_ATTN_XCD=0", names)
+
+
+@pytest.mark.parametrize("wgs", [1, 64])
+def test_swin_window_chunks_of_sixteen_hold_the_tight_bars(wgs):
+    """TFIMM_ATTN_WIN_WGS=1 / 64: attn_window_persist_kernel with up to 16 windows per chunk on batches of 2-5 -- chunks far
+    larger than the windows of a kind, half-filled last chunks"""
+    _attention_child(f"TFIMM_ATTN_WIN_WGS={wgs}", [n for n in _WINDOW_KERNEL_ROWS if n not in _B65])

@@ -498,9 +498,22 @@ _LAYOUTS = [("out_ldc_n8", _VEC), ("out_ldc_n4", _ANY), ("out_off2", _ANY), ("ou
 FAMILIES = {
     "vit_attention": [f"tight_attn_197_hd{hd}" for hd in (32, 48, 64, 80, 96, 128)] + [
         "tight_attn_65_tail1", "tight_attn_64_exact", "tight_attn_256_exact", "tight_attn_577_hd64", "tight_attn_197_spike",
-        "tight_attn_65_hd48_spike", "tight_attn_stream_197_multiround", "tight_attn_stream_129_spike"],
+        "tight_attn_65_hd48_spike", "tight_attn_stream_197_multiround", "tight_attn_stream_129_spike"] + [
+        # every kernel instantiation of the dispatcher (tests/test_attention_contract.py): head-dim edges, element loads / stores
+        "tight_attn_100_hd32", "tight_attn_40_hd32", "tight_attn_17_hd4", "tight_attn_300_hd32", "tight_attn_300_hd20"] + [
+        f"tight_attn_70_hd{hd}" for hd in ("1_h3", 8, 33, 40, 63, 65, 88, 97, 104, 127)] + [
+        "tight_attn_197_hd64_qkv_off8", "tight_attn_197_hd64_out_off4", "tight_attn_300_hd64_qkv_off8",
+        "tight_attn_stream_197_qkv_off8_stays_resident"],
     "swin_window_attention": [f"tight_swin_{s}" for s in _SWIN] + [f"tight_swin_tiles_{s}" for s in _SWIN] + [
-        "tight_swin_tiles_w7_shift3_56x56_b65_wpb2", "tight_swin_tiles_w7_noshift_56x56_b65_wpb2"],
+        "tight_swin_tiles_w7_shift3_56x56_b65_wpb2", "tight_swin_tiles_w7_noshift_56x56_b65_wpb2"] + [
+        # windows of 8 ... 17, head dims 8 ... 64 in windows, the 80 KiB limit, element loads
+        "tight_swin_w9_shift4_hd32", "tight_swin_tiles_w9_shift4_hd32", "tight_swin_tiles_w9_noshift_hd32",
+        "tight_swin_w11_shift5_hd32_lds_81352", "tight_swin_tiles_w11_shift5_hd32", "tight_swin_w7_shift3_hd64",
+        "tight_swin_tiles_w7_shift3_hd64", "tight_swin_w7_noshift_hd64", "tight_swin_w7_shift3_hd48", "tight_swin_tiles_w7_shift3_hd48",
+        "tight_swin_w7_shift3_hd33", "tight_swin_tiles_w7_shift3_hd8", "tight_swin_w9_shift4_hd64", "tight_swin_tiles_w9_shift4_hd64",
+        "tight_swin_tiles_w12_shift6_hd64", "tight_swin_w12_shift6_hd64", "tight_swin_w10_shift5_hd64_lds_84768",
+        "tight_swin_tiles_w16_shift8_hd32", "tight_swin_w17_shift8_34x34", "tight_swin_tiles_w17_shift8_34x34",
+        "tight_swin_tiles_w8_shift4_16x16", "tight_swin_tiles_w8_shift4_16x16_3heads", "tight_swin_tiles_w7_shift3_qkv_off8"],
     "cait": ["tight_tha_9_h1_hd32", "tight_tha_50_h6_hd48", "tight_tha_196_h4_hd48", "tight_tha_196_h4_hd48_by_value",
              "tight_tha_577_h4_hd48", "tight_tha_100_h16_hd48_by_value", "tight_tha_generic_16_h2_hd2", "tight_tha_generic_40_h5_hd24",
              "tight_class_attn_10_h2_hd32", "tight_class_attn_197_h4_hd48", "tight_class_attn_785_h16_hd48",
