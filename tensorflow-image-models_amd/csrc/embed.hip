@@ -15,7 +15,7 @@
 //   permuted identically on both operands so that within 64 columns lane (r, h) owns columns 32h .. 32h+31: it reads 64
 //   contiguous bytes of its row per four MFMA steps (the < 64 columns behind the last full group use the plain map).  The
 //   32 x 32 float32 tile has the query on the lane (column = lane & 31) and 16 gallery rows in the registers.  (The query
-//   tile and this loop are embed_score.h, shared with tfimm_hip_embed_search_wide, embed_wide.hip.)
+//   tile and this loop are embed_score.h, shared with the other gallery searches; the argument checks are embed_check.h.)
 //   Every (wave, query) owns a list of k (key, row) pairs in LDS, ordered by (key descending, row ascending) -- the keys of
 //   topk_select.h, 0 = empty.  A lane compares its 16 scores with the list's last entry and inserts the few that beat it; the
 //   two lanes of a query (h = 0, 1) take turns, so a list has one writer at a time.  The list is the k best of what the wave
@@ -29,6 +29,7 @@
 // No atomics, no scratch memory, every reduction in a fixed order; a score is a function of its query and its gallery row
 // alone (the k loop does not depend on B, chunk or the tile's other queries), and the selection is by a total order: results
 // are bit-reproducible and independent of B and chunk.
+#include "embed_check.h"
 #include "embed_score.h"
 #include "topk_select.h"
 
@@ -36,6 +37,7 @@ namespace {
 
 using namespace topk_sel;
 using namespace embed_score;
+using namespace embed_check;
 
 // ------------------------------------------------------------------------------------------------------------------------
 // l2_normalize
@@ -213,29 +215,30 @@ int choose_chunk(int B, int N, int k) {
 
 int pass1_lds_bytes(int E, int k, int list_waves) { return kQTile * query_pitch(E) + list_waves * kQTile * k * 8; }
 
-// validates (N, k, chunk) and resolves chunk = 0; returns an error text or nullptr
-const char* resolve_chunk(int B, int N, int E, int k, int* chunk, int64_t* chunks) {
-  if (E < TFIMM_EMBED_MIN_E || E > TFIMM_EMBED_MAX_E || E % 16 != 0) return "E";
-  if (N < 1) return "N";
-  if (k < 1 || k > N || k > TFIMM_EMBED_MAX_K) return "k";
-  if (*chunk < 0 || *chunk % kRowTile != 0) return "chunk";
-  if (B < 0 || B > TFIMM_EMBED_MAX_B) return "B";
-  if (*chunk == 0) *chunk = choose_chunk(B, N, k);
-  *chunks = cdiv64(N, *chunk);
-  if (*chunks * k > kPass2MaxCand) return "chunk";
-  return nullptr;
+constexpr const char* kFn = "embed_search";
+
+// a chunk of the wrong form, or one that leaves pass 2 more candidates than it holds
+int chunk_fail(int chunk, int N, int k) {
+  TFIMM_FAIL(TFIMM_EINVAL, "%s: chunk=%d, must be 0 or a positive multiple of 32 with ceil(N / chunk) * k <= %d (N=%d, k=%d)", kFn, chunk,
+             kPass2MaxCand, N, k);
 }
 
-int search_fail(const char* what, int B, int N, int E, int k, int chunk) {
-  if (what[0] == 'E')
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search: E=%d, must be a multiple of 16 in [%d, TFIMM_EMBED_MAX_E = %d]", E, TFIMM_EMBED_MIN_E, TFIMM_EMBED_MAX_E);
-  if (what[0] == 'N') TFIMM_FAIL(TFIMM_EINVAL, "embed_search: N=%d, must be in [1, 2^31)", N);
-  if (what[0] == 'k')
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search: k=%d, must be in [1, min(N = %d, TFIMM_EMBED_MAX_K = %d)]", k, N, TFIMM_EMBED_MAX_K);
-  if (what[0] == 'B') TFIMM_FAIL(TFIMM_EINVAL, "embed_search: B=%d, must be in [0, TFIMM_EMBED_MAX_B = %d]", B, TFIMM_EMBED_MAX_B);
-  TFIMM_FAIL(TFIMM_EINVAL, "embed_search: chunk=%d, must be 0 or a positive multiple of 32 with ceil(N / chunk) * k <= %d (N=%d, k=%d)",
-             chunk, kPass2MaxCand, N, k);
+// validates (B, N, E, k, chunk) and resolves chunk = 0; returns 0 or TFIMM_EINVAL with the message set
+int resolve_chunk(int B, int N, int E, int k, int* chunk, int64_t* chunks) {
+  TFIMM_EMBED_TRY(check_E(kFn, E));
+  TFIMM_EMBED_TRY(check_N(kFn, N));
+  if (k < 1 || k > N || k > TFIMM_EMBED_MAX_K)
+    TFIMM_FAIL(TFIMM_EINVAL, "%s: k=%d, must be in [1, min(N = %d, TFIMM_EMBED_MAX_K = %d)]", kFn, k, N, TFIMM_EMBED_MAX_K);
+  if (*chunk < 0 || *chunk % kRowTile != 0) return chunk_fail(*chunk, N, k);
+  TFIMM_EMBED_TRY(check_B(kFn, B));
+  if (*chunk == 0) *chunk = choose_chunk(B, N, k);
+  *chunks = cdiv64(N, *chunk);
+  if (*chunks * k > kPass2MaxCand) return chunk_fail(*chunk, N, k);
+  return 0;
 }
+
+// [B][chunks][k] keys and rows
+int64_t workspace_need(int B, int64_t chunks, int k) { return (int64_t)(B > 0 ? B : 1) * chunks * k * 8; }
 
 }  // namespace
 
@@ -255,31 +258,18 @@ extern "C" int tfimm_hip_l2_normalize(const float* x, int64_t ld_x, int B, int E
 
 extern "C" int64_t tfimm_hip_embed_search_workspace(int B, int N, int E, int k, int chunk) {
   int64_t chunks = 0;
-  const char* bad = resolve_chunk(B, N, E, k, &chunk, &chunks);
-  if (bad) return search_fail(bad, B, N, E, k, chunk);
-  return (int64_t)(B > 0 ? B : 1) * chunks * k * 8;
+  TFIMM_EMBED_TRY(resolve_chunk(B, N, E, k, &chunk, &chunks));
+  return workspace_need(B, chunks, k);
 }
 
 extern "C" int tfimm_hip_embed_search(const float* q, int64_t ld_q, int B, const void* g, int64_t ld_g, int N, int E, int k, int chunk,
                                       float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!q) TFIMM_FAIL(TFIMM_EINVAL, "embed_search: q is null");
-  if (!g) TFIMM_FAIL(TFIMM_EINVAL, "embed_search: g is null");
-  if (!scores) TFIMM_FAIL(TFIMM_EINVAL, "embed_search: scores is null");
-  if (!indices) TFIMM_FAIL(TFIMM_EINVAL, "embed_search: indices is null");
-  if (!workspace) TFIMM_FAIL(TFIMM_EINVAL, "embed_search: workspace is null");
-  if ((uintptr_t)g & 15) TFIMM_FAIL(TFIMM_EINVAL, "embed_search: g must be 16-byte aligned");
-  if (((uintptr_t)q | (uintptr_t)scores | (uintptr_t)indices | (uintptr_t)workspace) & 3)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search: q, scores, indices and workspace hold 4-byte elements and must be 4-byte aligned");
+  TFIMM_EMBED_TRY(check_pointers(kFn, {{"q", q, 4}, {"g", g, 16}, {"scores", scores, 4}, {"indices", indices, 4}, {"workspace", workspace, 4}}));
   int64_t chunks = 0;
-  const char* bad = resolve_chunk(B, N, E, k, &chunk, &chunks);
-  if (bad) return search_fail(bad, B, N, E, k, chunk);
-  if (ld_q < E) TFIMM_FAIL(TFIMM_EINVAL, "embed_search: ld_q=%lld is smaller than E=%d", (long long)ld_q, E);
-  if (ld_g < E || ld_g % 8 != 0)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search: ld_g=%lld, must be a multiple of 8 elements and at least E=%d", (long long)ld_g, E);
-  const int64_t need = (int64_t)(B > 0 ? B : 1) * chunks * k * 8;
-  if (workspace_bytes < need)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search: workspace_bytes=%lld, tfimm_hip_embed_search_workspace asks for %lld", (long long)workspace_bytes,
-               (long long)need);
+  TFIMM_EMBED_TRY(resolve_chunk(B, N, E, k, &chunk, &chunks));
+  TFIMM_EMBED_TRY(check_ld_q(kFn, ld_q, E));
+  TFIMM_EMBED_TRY(check_ld_g(kFn, ld_g, E));
+  TFIMM_EMBED_TRY(check_workspace(kFn, workspace_bytes, workspace_need(B, chunks, k)));
   if (B == 0) return 0;
 
   // as many list-keeping waves as LDS allows next to the query tile: 4, else 2, else 1 (E = 2048 with k > 32 only)

@@ -19,13 +19,14 @@
 //   (v_mfma_f32_32x32x16_fp8_fp8, same shape, operand map and C/D layout as the bf16 instruction of embed_score.h; lane (r, h)
 //   holds 8 contiguous bytes); key = acc * 2^(e_row).  The query's exponent is a positive constant per query and is not applied.
 //
-//   Pass 1 is the grid, the query tile and the buffer selection of embed_wide.hip (embed_buffer.h) with k = candidates and a
-//   new score tile: the query tile lives in LDS as fp8, row pitch E + 16 bytes, count / threshold / flags in the 16 bytes
-//   behind a row; within 64 columns lane (r, h) owns bytes 32h .. 32h+31 of its row: two 16-byte loads for four MFMAs, the
-//   same permutation on both operands (the < 64 columns behind the last full group use the plain map, 8 bytes per lane).  The
-//   loads of the next 64 columns -- of the next tile behind the last group of this one, across the step's barrier and the
-//   selection -- are issued before the MFMAs of the current ones.  The 16 row exponents of a lane's registers are four aligned
-//   4-byte loads, applied before the threshold test.  LDS is 32 (E + 16) + 32 * 8 * cap bytes.
+//   Pass 1 is the grid and the buffer selection of embed_wide.hip -- BufferTile, buffered_steps and emit_pairs of embed_buffer.h
+//   -- with k = candidates; what is its own is the score of a step: the query tile lives in LDS as fp8, row pitch E + 16 bytes,
+//   count / threshold / flags in the 16 bytes behind a row; within 64 columns lane (r, h) owns bytes 32h .. 32h+31 of its row:
+//   two 16-byte loads for four MFMAs, the same permutation on both operands (the < 64 columns behind the last full group use
+//   the plain map, 8 bytes per lane).  The loads of the next 64 columns -- of the next tile behind the last group of this one,
+//   across the step's barrier and the selection -- are issued before the MFMAs of the current ones; the registers that hold
+//   them live in the kernel and the score callable works on them.  The 16 row exponents of a lane's registers are four
+//   aligned 4-byte loads, applied inside the callable: the loop sees final keys.  LDS is 32 (E + 16) + 32 * 8 * cap bytes.
 //   Pass 2 is select_pass2: chunks * candidates pairs -> the `candidates` best rows per query.
 //   Pass 3, one workgroup per query: the query rounded to bf16 in LDS; its candidates 32 at a time through score_tile, lane r's
 //   row pointer being candidate r and every column of the B operand the one query (all lanes read the same LDS row), so the
@@ -120,11 +121,6 @@ struct CoarseArgs {
   int64_t ld_q, ld_c;
   int B, N, E, c, chunk, chunks, cap;
 };
-
-// the four words behind the codes of query row qi of the tile: count, threshold key, threshold row, and (rows 0 .. 2) a flag
-__device__ __forceinline__ int* tile_meta(unsigned char* smem, int pitch, int E, int qi) {
-  return reinterpret_cast<int*>(smem + (size_t)qi * pitch + E);
-}
 
 // queries q0 .. q0 + 31 -> bf16 -> fp8 codes in smem (queries past B: zeros), a wave per query; the caller places the barrier
 __device__ __forceinline__ void load_query_codes(unsigned char* smem, const float* q, int64_t ld_q, int q0, int B, int E, int lane,
@@ -222,33 +218,24 @@ __device__ __forceinline__ f32x16 held_tile(const uint4 (&t)[2 * G], const unsig
 template <int G>
 __global__ void __launch_bounds__(kThreads, G == 8 ? 2 : 3) embed_coarse_pass1(CoarseArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int E = a.E, k = a.c, cap = a.cap;
-  const int pitch = code_pitch(E);
-  uint32_t* buf_key = reinterpret_cast<uint32_t*>(smem + (size_t)kQTile * pitch);   // [32][cap]
-  int* buf_idx = reinterpret_cast<int*>(buf_key + kQTile * cap);                   // [32][cap]
+  const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
+  const int E = a.E, k = a.c;
+  const BufferTile t(smem, code_pitch(E), E, a.cap);
   const int q0 = blockIdx.y * kQTile;
+  const int occ = min(kQTile, a.B - q0);                // lanes 0 .. occ - 1 hold a query
 
   load_query_codes(smem, a.q, a.ld_q, q0, a.B, E, lane, wave);
-  if (tid < kQTile) {
-    int* m = tile_meta(smem, pitch, E, tid);
-    m[0] = 0;
-    m[1] = (int)kRetired;
-    m[2] = INT_MAX;
-    m[3] = 0;
-  }
+  t.clear(tid);
   __syncthreads();
 
   const int64_t row_begin = (int64_t)blockIdx.x * a.chunk;
   const int64_t row_end = min(row_begin + (int64_t)a.chunk, (int64_t)a.N);
   const int r = lane & 31, h = lane >> 5;
-  const bool q_valid = q0 + r < a.B;
   const int groups = E / 64, tail = (E % 64) / 16;
-  const unsigned char* qrow = smem + (size_t)r * pitch;
-  const Buffer mine = {buf_key + r * cap, buf_idx + r * cap, tile_meta(smem, pitch, E, r), cap, r};
-  const int steps = (int)((row_end - row_begin + kStepRows - 1) / kStepRows);
+  const unsigned char* qrow = smem + (size_t)r * t.pitch;
 
-  // a row past the gallery reads the last row instead (its sums are never looked at)
+  // the wave's first tile, loaded ahead of the loop.  A row past the gallery reads the last row instead (its sums are never
+  // looked at).
   const int64_t first = row_begin + wave * kRowTile;
   constexpr int kHeld = G > 0 ? 2 * G : 2;
   uint4 cur[kHeld];
@@ -264,85 +251,47 @@ __global__ void __launch_bounds__(kThreads, G == 8 ? 2 : 3) embed_coarse_pass1(C
     }
   }
 
-  int f = 0;                                           // this step's flag: step mod 3
-  for (int s = 0; s < steps; ++s) {
-    int* flag = tile_meta(smem, pitch, E, f) + 3;
-    const int fn = f == 2 ? 0 : f + 1;
-    if (tid == 0) tile_meta(smem, pitch, E, fn)[3] = 0;          // the next step's: last read behind the barrier before last
-    const int64_t base = row_begin + (int64_t)s * kStepRows + wave * kRowTile;
-    if (base < row_end) {
-      const unsigned char* ca = a.codes + min(base + r, (int64_t)a.N - 1) * a.ld_c;
-      const int64_t nbase = base + kStepRows;
-      const unsigned char* next = nbase < row_end ? a.codes + min(nbase + r, (int64_t)a.N - 1) * a.ld_c : ca;
-      // the exponents of rows base + 8 j + 4 h .. + 3: one aligned word each (base is a multiple of 32); bytes past N are not read
-      uint32_t ew[4];
+  // the coarse keys of a step: the code sums of the tile in `cur` -- while the loads of the wave's next tile, which outlive the
+  // step's barrier and the selection, are in flight -- times 2^(e_row)
+  buffered_steps(t, row_begin, row_end, occ, k, [&](int64_t base) {
+    const unsigned char* ca = a.codes + min(base + r, (int64_t)a.N - 1) * a.ld_c;
+    const int64_t nbase = base + kStepRows;
+    const unsigned char* next = nbase < row_end ? a.codes + min(nbase + r, (int64_t)a.N - 1) * a.ld_c : ca;
+    // the exponents of rows base + 8 j + 4 h .. + 3: one aligned word each (base is a multiple of 32); bytes past N are not read
+    uint32_t ew[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int64_t at = base + 8 * j + 4 * h;
-        ew[j] = 0;
-        if (at + 3 < a.N) {
-          ew[j] = *reinterpret_cast<const uint32_t*>(a.exps + at);
-        } else {
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (at + u < a.N) ew[j] |= (uint32_t)(unsigned char)a.exps[at + u] << (8 * u);
-        }
-      }
-      f32x16 acc;
-      if constexpr (G > 0) {
-        uint4 nxt[kHeld];
-#pragma unroll
-        for (int i = 0; i < kHeld; ++i) nxt[i] = cur[i];
-        if (nbase < row_end) load_held<G>(nxt, next, h, groups);
-        acc = held_tile<G>(cur, ca, qrow, h, groups, tail);
-#pragma unroll
-        for (int i = 0; i < kHeld; ++i) cur[i] = nxt[i];
+    for (int j = 0; j < 4; ++j) {
+      const int64_t at = base + 8 * j + 4 * h;
+      ew[j] = 0;
+      if (at + 3 < a.N) {
+        ew[j] = *reinterpret_cast<const uint32_t*>(a.exps + at);
       } else {
-        acc = coarse_tile(ca, next, qrow, h, groups, tail, cur[0], cur[1]);
-      }
-      // ---- lane (r, h): query q0 + r, gallery rows base + (i & 3) + 8 (i >> 2) + 4 h
-      if (q_valid) {
-        const uint32_t tk = (uint32_t)mine.meta[1];
-        const int ti = mine.meta[2];
-        int top = 0;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int64_t row = base + (i & 3) + 8 * (i >> 2) + 4 * h;
-          int e = (int)(signed char)(ew[i >> 2] >> (8 * (i & 3)));
-          e = e < kExpMin ? kExpMin : (e > kExpMax ? kExpMax : e);        // whatever the bytes are, a float32 factor
-          const uint32_t key = key_of(__float_as_uint(acc[i] * pow2(e)));
-          if (row < row_end && beats(key, (int)row, tk, ti)) top = buffer_append(mine, key, (int)row);
-        }
-        if (top > cap - kStepRows) *flag = 1;          // the next step could overflow this buffer
+        for (int u = 0; u < 4; ++u)
+          if (at + u < a.N) ew[j] |= (uint32_t)(unsigned char)a.exps[at + u] << (8 * u);
       }
     }
-    __syncthreads();
-    if (*flag) {                                       // written before the barrier, cleared two steps on: one value for all
-      for (int qi = wave; qi < kQTile; qi += kWaves) {
-        const Buffer b = {buf_key + qi * cap, buf_idx + qi * cap, tile_meta(smem, pitch, E, qi), cap, qi};
-        prune_to_k<kMaxCap / 64>(b, k, lane);
-      }
-      __syncthreads();
+    f32x16 acc;
+    if constexpr (G > 0) {
+      uint4 nxt[kHeld];
+#pragma unroll
+      for (int i = 0; i < kHeld; ++i) nxt[i] = cur[i];
+      if (nbase < row_end) load_held<G>(nxt, next, h, groups);
+      acc = held_tile<G>(cur, ca, qrow, h, groups, tail);
+#pragma unroll
+      for (int i = 0; i < kHeld; ++i) cur[i] = nxt[i];
+    } else {
+      acc = coarse_tile(ca, next, qrow, h, groups, tail, cur[0], cur[1]);
     }
-    f = fn;
-  }
-  for (int qi = wave; qi < kQTile; qi += kWaves) {
-    const Buffer b = {buf_key + qi * cap, buf_idx + qi * cap, tile_meta(smem, pitch, E, qi), cap, qi};
-    prune_to_k<kMaxCap / 64>(b, k, lane);
-  }
-  __syncthreads();
-
-  // ---- c pairs per query, unsorted; an empty entry (a chunk of fewer than c rows): key 0, row INT_MAX
-  for (int i = tid; i < kQTile * k; i += kThreads) {
-    const int qi = i / k, j = i - qi * k;
-    if (q0 + qi >= a.B) continue;
-    const Buffer b = {buf_key + qi * cap, buf_idx + qi * cap, tile_meta(smem, pitch, E, qi), cap, qi};
-    const int n = min(b.meta[0], k);
-    const int p = slot_at(b, j);
-    const int64_t out = ((int64_t)(q0 + qi) * a.chunks + blockIdx.x) * k + j;
-    a.ws_key[out] = j < n ? b.key[p] : kRetired;
-    a.ws_idx[out] = j < n ? b.idx[p] : INT_MAX;
-  }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      int e = (int)(signed char)(ew[i >> 2] >> (8 * (i & 3)));
+      e = e < kExpMin ? kExpMin : (e > kExpMax ? kExpMax : e);        // whatever the bytes are, a float32 factor
+      acc[i] *= pow2(e);
+    }
+    return acc;
+  });
+  emit_pairs(t, occ, k, a.ws_key, a.ws_idx, [&](int qi) { return ((int64_t)(q0 + qi) * a.chunks + blockIdx.x) * k; });
 }
 
 __global__ void __launch_bounds__(kThreads) embed_coarse_pass2(SelectArgs a) { select_pass2(a); }
@@ -404,39 +353,25 @@ __global__ void __launch_bounds__(kThreads) embed_coarse_rerank(RerankArgs a) {
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
-// what the LDS next to an fp8 query tile holds: 32 (E + 16) + 32 * 8 * cap <= 160 KiB with cap >= candidates + 128
-int max_candidates(int E) {
-  if (E < TFIMM_EMBED_MIN_E || E > TFIMM_EMBED_MAX_E || E % 16 != 0) return 0;
-  const int m = (kLdsBudget - kQTile * code_pitch(E)) / (kQTile * 8) - kStepRows;
-  return m > TFIMM_EMBED_COARSE_MAX_CANDIDATES ? TFIMM_EMBED_COARSE_MAX_CANDIDATES : m;
-}
+constexpr const char* kFn = "embed_search_coarse";
 
-// validates (B, N, E, k, candidates, chunk) and resolves chunk = 0; returns what is wrong or nullptr
-const char* resolve(int B, int N, int E, int k, int c, int* chunk, int64_t* chunks) {
-  if (E < TFIMM_EMBED_MIN_E || E > TFIMM_EMBED_MAX_E || E % 16 != 0) return "E";
-  if (N < 1) return "N";
-  if (c < 1 || c > N || c > max_candidates(E)) return "candidates";
-  if (k < 1 || k > c) return "k";
-  if (*chunk < 0 || *chunk % kRowTile != 0) return "chunk";
-  if (B < 0 || B > TFIMM_EMBED_MAX_B) return "B";
+// what the LDS next to an fp8 query tile holds: 32 (E + 16) + 32 * 8 * cap <= 160 KiB with cap >= candidates + 128
+int max_candidates(int E) { return e_ok(E) ? fit_max_k(kQTile * code_pitch(E), TFIMM_EMBED_COARSE_MAX_CANDIDATES) : 0; }
+
+// validates (B, N, E, k, candidates, chunk) and resolves chunk = 0; returns 0 or TFIMM_EINVAL with the message set
+int resolve(int B, int N, int E, int k, int c, int* chunk, int64_t* chunks) {
+  TFIMM_EMBED_TRY(check_E(kFn, E));
+  TFIMM_EMBED_TRY(check_N(kFn, N));
+  if (c < 1 || c > N || c > max_candidates(E))
+    TFIMM_FAIL(TFIMM_EINVAL, "%s: candidates=%d, must be in [1, min(N = %d, tfimm_hip_embed_search_coarse_max_candidates(%d) = %d)]", kFn, c,
+               N, E, max_candidates(E));
+  if (k < 1 || k > c) TFIMM_FAIL(TFIMM_EINVAL, "%s: k=%d, must be in [1, candidates = %d]", kFn, k, c);
+  TFIMM_EMBED_TRY(check_chunk(kFn, *chunk));
+  TFIMM_EMBED_TRY(check_B(kFn, B));
   // every chunk hands `candidates` pairs to pass 2, which one workgroup per query reads: at least 16 times as many rows
   if (*chunk == 0) *chunk = choose_chunk(B, N, c, 16);
   *chunks = cdiv64(N, *chunk);
-  return nullptr;
-}
-
-int coarse_fail(const char* what, int B, int N, int E, int k, int c, int chunk) {
-  if (what[0] == 'E')
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: E=%d, must be a multiple of 16 in [%d, TFIMM_EMBED_MAX_E = %d]", E,
-               TFIMM_EMBED_MIN_E, TFIMM_EMBED_MAX_E);
-  if (what[0] == 'N') TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: N=%d, must be in [1, 2^31)", N);
-  if (what[0] == 'c' && what[1] == 'a')
-    TFIMM_FAIL(TFIMM_EINVAL,
-               "embed_search_coarse: candidates=%d, must be in [1, min(N = %d, tfimm_hip_embed_search_coarse_max_candidates(%d) = %d)]", c,
-               N, E, max_candidates(E));
-  if (what[0] == 'k') TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: k=%d, must be in [1, candidates = %d]", k, c);
-  if (what[0] == 'B') TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: B=%d, must be in [0, TFIMM_EMBED_MAX_B = %d]", B, TFIMM_EMBED_MAX_B);
-  TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: chunk=%d, must be 0 or a positive multiple of 32", chunk);
+  return 0;
 }
 
 // [B][chunks][c] keys and rows of pass 1, [B][c] keys and rows of pass 2
@@ -446,18 +381,12 @@ int64_t workspace_need(int B, int64_t chunks, int c) { return (int64_t)(B > 0 ? 
 
 extern "C" int tfimm_hip_embed_quantize_rows(const void* g, int64_t ld_g, int N, int E, void* codes, int64_t ld_c, int8_t* exps,
                                              void* stream) {
-  if (!g) TFIMM_FAIL(TFIMM_EINVAL, "embed_quantize_rows: g is null");
-  if (!codes) TFIMM_FAIL(TFIMM_EINVAL, "embed_quantize_rows: codes is null");
-  if (!exps) TFIMM_FAIL(TFIMM_EINVAL, "embed_quantize_rows: exps is null");
-  if (((uintptr_t)g | (uintptr_t)codes) & 15) TFIMM_FAIL(TFIMM_EINVAL, "embed_quantize_rows: g and codes must be 16-byte aligned");
-  if (E < TFIMM_EMBED_MIN_E || E > TFIMM_EMBED_MAX_E || E % 16 != 0)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_quantize_rows: E=%d, must be a multiple of 16 in [%d, TFIMM_EMBED_MAX_E = %d]", E, TFIMM_EMBED_MIN_E,
-               TFIMM_EMBED_MAX_E);
-  if (N < 0) TFIMM_FAIL(TFIMM_EINVAL, "embed_quantize_rows: N=%d, must be in [0, 2^31)", N);
-  if (ld_g < E || ld_g % 8 != 0)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_quantize_rows: ld_g=%lld, must be a multiple of 8 elements and at least E=%d", (long long)ld_g, E);
-  if (ld_c < E || ld_c % 16 != 0)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_quantize_rows: ld_c=%lld, must be a multiple of 16 bytes and at least E=%d", (long long)ld_c, E);
+  constexpr const char* fn = "embed_quantize_rows";
+  TFIMM_EMBED_TRY(check_pointers(fn, {{"g", g, 16}, {"codes", codes, 16}, {"exps", exps, 1}}));
+  TFIMM_EMBED_TRY(check_E(fn, E));
+  if (N < 0) TFIMM_FAIL(TFIMM_EINVAL, "%s: N=%d, must be in [0, 2^31)", fn, N);
+  TFIMM_EMBED_TRY(check_ld_g(fn, ld_g, E));
+  TFIMM_EMBED_TRY(check_ld_c(fn, ld_c, E));
   if (N == 0) return 0;
   TFIMM_LAUNCH(embed_quantize_rows, dim3((unsigned)cdiv64(N, kWaves)), dim3(kThreads), 0, (hipStream_t)stream,
                reinterpret_cast<const uint16_t*>(g), ld_g, N, E, reinterpret_cast<unsigned char*>(codes), ld_c,
@@ -469,36 +398,23 @@ extern "C" int tfimm_hip_embed_search_coarse_max_candidates(int E) { return max_
 
 extern "C" int64_t tfimm_hip_embed_search_coarse_workspace(int B, int N, int E, int k, int candidates, int chunk) {
   int64_t chunks = 0;
-  const char* bad = resolve(B, N, E, k, candidates, &chunk, &chunks);
-  if (bad) return coarse_fail(bad, B, N, E, k, candidates, chunk);
+  TFIMM_EMBED_TRY(resolve(B, N, E, k, candidates, &chunk, &chunks));
   return workspace_need(B, chunks, candidates);
 }
 
 extern "C" int tfimm_hip_embed_search_coarse(const float* q, int64_t ld_q, int B, const void* g, int64_t ld_g, const void* codes,
                                              int64_t ld_c, const int8_t* exps, int N, int E, int k, int candidates, int chunk,
                                              float* scores, int32_t* indices, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!q) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: q is null");
-  if (!g) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: g is null");
-  if (!codes) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: codes is null");
-  if (!exps) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: exps is null");
-  if (!scores) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: scores is null");
-  if (!indices) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: indices is null");
-  if (!workspace) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: workspace is null");
-  if (((uintptr_t)g | (uintptr_t)codes) & 15) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: g and codes must be 16-byte aligned");
-  if (((uintptr_t)q | (uintptr_t)exps | (uintptr_t)scores | (uintptr_t)indices | (uintptr_t)workspace) & 3)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: q, exps, scores, indices and workspace must be 4-byte aligned");
+  TFIMM_EMBED_TRY(check_pointers(kFn,
+                                 {{"q", q, 4}, {"g", g, 16}, {"codes", codes, 16}, {"exps", exps, 4}, {"scores", scores, 4},
+                                  {"indices", indices, 4}, {"workspace", workspace, 4}},
+                                 "must be 4-byte aligned"));
   int64_t chunks = 0;
-  const char* bad = resolve(B, N, E, k, candidates, &chunk, &chunks);
-  if (bad) return coarse_fail(bad, B, N, E, k, candidates, chunk);
-  if (ld_q < E) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: ld_q=%lld is smaller than E=%d", (long long)ld_q, E);
-  if (ld_g < E || ld_g % 8 != 0)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: ld_g=%lld, must be a multiple of 8 elements and at least E=%d", (long long)ld_g, E);
-  if (ld_c < E || ld_c % 16 != 0)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: ld_c=%lld, must be a multiple of 16 bytes and at least E=%d", (long long)ld_c, E);
-  const int64_t need = workspace_need(B, chunks, candidates);
-  if (workspace_bytes < need)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_coarse: workspace_bytes=%lld, tfimm_hip_embed_search_coarse_workspace asks for %lld",
-               (long long)workspace_bytes, (long long)need);
+  TFIMM_EMBED_TRY(resolve(B, N, E, k, candidates, &chunk, &chunks));
+  TFIMM_EMBED_TRY(check_ld_q(kFn, ld_q, E));
+  TFIMM_EMBED_TRY(check_ld_g(kFn, ld_g, E));
+  TFIMM_EMBED_TRY(check_ld_c(kFn, ld_c, E));
+  TFIMM_EMBED_TRY(check_workspace(kFn, workspace_bytes, workspace_need(B, chunks, candidates)));
   if (B == 0) return 0;
 
   static tfimm_once_t ready;

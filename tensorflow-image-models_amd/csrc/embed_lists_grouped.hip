@@ -5,8 +5,8 @@
 // a prune is a function of what it has seen (embed_buffer.h) -- and the second pass is the same select_pass2.  Only the work per
 // byte read changes: embed_lists_pass1 fills all 32 columns of the MFMA's B operand with one query, this kernel with 32.
 //
-//   A PAIR is (query b, probe slot s), p = b * nprobe + s, P = B * nprobe of them.  It is LIVE when its list l = probes[b][s] is in
-//   [0, L), no earlier slot of the query names l, and the list is not empty (offsets clamped to [0, N]).
+//   A PAIR is (query b, probe slot s), p = b * nprobe + s, P = B * nprobe of them.  It is LIVE by the rule of embed_lists.h, which
+//   also holds the cut of a list into parts and the empty entries: one text for both searches over lists.
 //
 //   Grouping, four small launches over tables in the workspace:
 //     grouped_fill   count[0 : L] = 0, and every query's k outputs "none" (-1, -inf): pass 2 writes the survivors only.
@@ -22,45 +22,30 @@
 //   T_max = min(P / 32 + min(L, P), min(L, P) * ceil(B / 32)) -- a list counts once per query and the counts sum to at most P --
 //   and a workgroup whose tile is not below first[L] returns at once.  A workgroup owns one (tile, part): it gathers its up to
 //   32 queries through `members` into the query tile of embed_score.h (an unoccupied lane: zeros, and it never appends), takes
-//   cut `part` of the tile's list by embed_lists_pass1's formula, and runs embed_wide_pass1's step loop over those rows: four
-//   waves, one score_tile per wave and step with the query on the lane, one buffer per query keyed by (score key, POSITION),
-//   the three rotating flags, prune_to_k by the waves in turn, cap = choose_cap(...).  Then each occupied lane's k pairs go to
-//   workspace[b][s * parts + part][k], ids[pos] in place of the position; a workgroup whose cut is empty writes k empty entries
+//   cut `part` of the tile's list, and runs buffered_steps of embed_buffer.h over those positions with score_tile as the score
+//   of a step: one buffer per query keyed by (score key, POSITION), cap = choose_cap(...).  Then emit_pairs: each occupied
+//   lane's k pairs go to workspace[b][s * parts + part][k], ids[pos] in place of the position; a workgroup whose cut is empty writes k empty entries
 //   for each member.  Every (query, slot, part) is written by exactly one workgroup or by grouped_place, in every call.
 //   LDS is 32 (2 E + 16) + 32 * 8 * cap bytes, as in embed_wide.hip: hence k <= tfimm_hip_embed_search_wide_max_k(E).
 //
 //   Pass 2, one workgroup per query: select_pass2 of embed_buffer.h over the nprobe * parts * k pairs, unchanged.
-#include "embed_buffer.h"
+#include "embed_lists.h"
 
 namespace {
 
-using namespace embed_buffer;
+using namespace embed_lists;
 
-constexpr int kMaxParts = 64;
-constexpr int kMaxB = 65535;
+constexpr const char* kFn = "embed_search_lists_grouped";
 constexpr int kPlaceThreads = 32;                         // threads per pair of grouped_place
-static_assert((int64_t)kMaxB * TFIMM_EMBED_LISTS_MAX_PROBE < (1ll << 31), "a pair number is an int");
 
-struct GroupArgs {
-  const float* q;
-  const uint16_t* g;         // rows in list order
-  const int32_t* ids;        // [N]
-  const int32_t* offsets;    // [L + 1]
-  const int32_t* probes;     // [B][ld_p]
-  uint32_t* ws_key;          // [B][nprobe * parts][k]
-  int32_t* ws_idx;           // [B][nprobe * parts][k]
+struct GroupArgs : ListsArgs {
   int32_t* count;            // [L]         live pairs per list
   int32_t* first;            // [L + 1]     first tile per list; [L]: the number of tiles
   int32_t* rank;             // [P]         of a live pair among those of its list, -1: not live
   int32_t* tile_list;        // [T_max]
   int32_t* members;          // [T_max][32] pair numbers
-  uint32_t* scores;          // float32 bits [B][k]
-  int32_t* indices;          // [B][k]
-  int64_t ld_q, ld_g, ld_p;
-  int B, N, E, L, nprobe, k, parts, cap, P, tmax;
+  int B, P, tmax;
 };
-
-__device__ __forceinline__ int clamp_pos(int v, int N) { return v < 0 ? 0 : (v > N ? N : v); }
 
 __global__ void __launch_bounds__(kThreads) grouped_fill(GroupArgs a) {
   const int64_t step = (int64_t)gridDim.x * kThreads, outs = (int64_t)a.B * a.k;
@@ -75,12 +60,8 @@ __global__ void __launch_bounds__(kThreads) grouped_rank(GroupArgs a) {
   const int p = blockIdx.x * kThreads + threadIdx.x;
   if (p >= a.P) return;
   const int b = p / a.nprobe, s = p - b * a.nprobe;
-  const int32_t* mine = a.probes + (int64_t)b * a.ld_p;
-  const int l = mine[s];
-  bool live = l >= 0 && l < a.L;
-  for (int e = 0; e < s && live; ++e) live = mine[e] != l;                 // a repeated list counts once
-  if (live) live = clamp_pos(a.offsets[l + 1], a.N) > clamp_pos(a.offsets[l], a.N);
-  a.rank[p] = live ? atomicAdd(a.count + l, 1) : -1;
+  const int32_t* probes = a.probes + (int64_t)b * a.ld_p;
+  a.rank[p] = live_pair(a, probes, s) ? atomicAdd(a.count + probes[s], 1) : -1;
 }
 
 // one workgroup: the exclusive scan of ceil(count / 32) over the lists, thread t taking a run of ceil(L / 256) lists
@@ -124,137 +105,54 @@ __global__ void __launch_bounds__(kThreads) grouped_place(GroupArgs a) {
     }
     return;
   }
-  const int64_t out = (int64_t)p * a.parts * a.k;
-  for (int j = t; j < a.parts * a.k; j += kPlaceThreads) {
-    a.ws_key[out + j] = kRetired;
-    a.ws_idx[out + j] = INT_MAX;
-  }
-}
-
-// the four words behind query row qi of the tile: count, threshold key, threshold row, and (rows 0 .. 2) a step's flag
-__device__ __forceinline__ int* tile_meta(unsigned char* smem, int pitch, int E, int qi) {
-  return reinterpret_cast<int*>(smem + (size_t)qi * pitch + 2 * E);
+  empty_entries(a, (int64_t)p * a.parts * a.k, a.parts * a.k, t, kPlaceThreads);
 }
 
 __global__ void __launch_bounds__(kThreads) embed_lists_grouped_pass1(GroupArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int E = a.E, k = a.k, cap = a.cap;
+  const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
+  const int E = a.E, k = a.k;
   const int tile = blockIdx.x, part = blockIdx.y;
   if (tile >= a.first[a.L]) return;                      // the grid is the bound T_max
   const int l = a.tile_list[tile];
   if (l < 0 || l >= a.L) return;                         // (never: the test keeps a broken invariant from reading)
   const int occ = max(0, min(kQTile, a.count[l] - (tile - a.first[l]) * kQTile));      // lanes 0 .. occ - 1 hold a query
   const int32_t* members = a.members + (int64_t)tile * kQTile;
+  // where member qi's pairs of this part go; a pair number outside the table (never) writes nothing
+  const auto out = [&](int qi) {
+    const int p = members[qi];
+    return p < 0 || p >= a.P ? (int64_t)-1 : ((int64_t)p * a.parts + part) * k;
+  };
 
-  // ---- this workgroup's rows: positions [begin, end) of the list order, embed_lists_pass1's cut; the same in every thread
-  const int lo = clamp_pos(a.offsets[l], a.N), hi = clamp_pos(a.offsets[l + 1], a.N);
-  int64_t begin = 0, end = 0;
-  if (hi > lo) {
-    const int64_t per = ((int64_t)(hi - lo) + a.parts - 1) / a.parts;
-    begin = min((int64_t)lo + part * per, (int64_t)hi);
-    end = min(begin + per, (int64_t)hi);
-  }
-  if (end <= begin) {                                    // a part behind the list's last row: k empty entries per member
-    for (int qi = wave; qi < occ; qi += kWaves) {
-      const int p = members[qi];
-      if (p < 0 || p >= a.P) continue;
-      const int64_t out = ((int64_t)p * a.parts + part) * k;
-      for (int j = lane; j < k; j += 64) {
-        a.ws_key[out + j] = kRetired;
-        a.ws_idx[out + j] = INT_MAX;
-      }
-    }
+  // ---- this workgroup's rows: positions [begin, end) of the list order; the same in every thread
+  const Cut cut = list_cut(a, l, part);
+  if (cut.end <= cut.begin) {                            // a part behind the list's last row: k empty entries per member
+    for (int qi = wave; qi < occ; qi += kWaves)
+      if (out(qi) >= 0) empty_entries(a, out(qi), k, lane, 64);
     return;
   }
 
   // ---- the query tile, gathered: a wave takes a row at a time (its query is a scalar), the lanes two values each
-  const int pitch = query_pitch(E);
-  uint32_t* buf_key = reinterpret_cast<uint32_t*>(smem + (size_t)kQTile * pitch);   // [32][cap]
-  int* buf_idx = reinterpret_cast<int*>(buf_key + kQTile * cap);                   // [32][cap]
+  const BufferTile t(smem, query_pitch(E), 2 * E, a.cap);
   for (int qi = wave; qi < kQTile; qi += kWaves) {
     const int p = qi < occ ? members[qi] : -1;
     const float* src = p >= 0 && p < a.P ? a.q + (int64_t)(p / a.nprobe) * a.ld_q : nullptr;
-    uint32_t* dst = reinterpret_cast<uint32_t*>(smem + (size_t)qi * pitch);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(smem + (size_t)qi * t.pitch);
     for (int i = lane; i < E / 2; i += 64)
       dst[i] = src ? bf16_rne(__float_as_uint(src[2 * i])) | (bf16_rne(__float_as_uint(src[2 * i + 1])) << 16) : 0u;
   }
-  if (tid < kQTile) {
-    int* m = tile_meta(smem, pitch, E, tid);
-    m[0] = 0;
-    m[1] = (int)kRetired;
-    m[2] = INT_MAX;
-    m[3] = 0;
-  }
+  t.clear(tid);
   __syncthreads();
 
   const int r = lane & 31, h = lane >> 5;
-  const bool q_valid = r < occ;
   const int groups = E / 64, tail = (E % 64) / 16;
-  const unsigned char* qrow = smem + (size_t)r * pitch;
-  const Buffer mine = {buf_key + r * cap, buf_idx + r * cap, tile_meta(smem, pitch, E, r), cap, r};
-  const int steps = (int)((end - begin + kStepRows - 1) / kStepRows);
-
-  int f = 0;                                             // this step's flag: step mod 3
-  for (int s = 0; s < steps; ++s) {
-    int* flag = tile_meta(smem, pitch, E, f) + 3;
-    const int fn = f == 2 ? 0 : f + 1;
-    if (tid == 0) tile_meta(smem, pitch, E, fn)[3] = 0;  // the next step's: last read behind the barrier before last
-    const int64_t base = begin + (int64_t)s * kStepRows + wave * kRowTile;
-    if (base < end) {
-      // a tile row past the cut reads row min(.., N - 1) instead (its scores are never looked at)
-      const int64_t grow = min(base + r, (int64_t)a.N - 1);
-      const f32x16 acc = score_tile(a.g + grow * a.ld_g, qrow, h, groups, tail);
-      // ---- lane (r, h): member r, positions base + (i & 3) + 8 (i >> 2) + 4 h
-      if (q_valid) {
-        const uint32_t tk = (uint32_t)mine.meta[1];
-        const int ti = mine.meta[2];
-        int top = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int64_t pos = base + (i & 3) + 8 * (i >> 2) + 4 * h;
-          const uint32_t key = key_of(__float_as_uint(acc[i]));
-          if (pos < end && beats(key, (int)pos, tk, ti)) top = buffer_append(mine, key, (int)pos);
-        }
-        if (top > cap - kStepRows) *flag = 1;            // the next step could overflow this buffer
-      }
-    }
-    __syncthreads();
-    if (*flag) {                                         // written before the barrier, cleared two steps on: one value for all
-      for (int qi = wave; qi < occ; qi += kWaves) {
-        const Buffer b = {buf_key + qi * cap, buf_idx + qi * cap, tile_meta(smem, pitch, E, qi), cap, qi};
-        prune_to_k<kMaxCap / 64>(b, k, lane);
-      }
-      __syncthreads();
-    }
-    f = fn;
-  }
-  for (int qi = wave; qi < occ; qi += kWaves) {
-    const Buffer b = {buf_key + qi * cap, buf_idx + qi * cap, tile_meta(smem, pitch, E, qi), cap, qi};
-    prune_to_k<kMaxCap / 64>(b, k, lane);
-  }
-  __syncthreads();
-
-  // ---- k pairs per member, unsorted, the original row in place of the position; an empty entry: key 0, row INT_MAX
-  for (int qi = wave; qi < occ; qi += kWaves) {
-    const int p = members[qi];
-    if (p < 0 || p >= a.P) continue;
-    const Buffer b = {buf_key + qi * cap, buf_idx + qi * cap, tile_meta(smem, pitch, E, qi), cap, qi};
-    const int n = min(b.meta[0], k);
-    const int64_t out = ((int64_t)p * a.parts + part) * k;
-    for (int j = lane; j < k; j += 64) {
-      uint32_t key = kRetired;
-      int id = INT_MAX;
-      if (j < n) {
-        const int at = slot_at(b, j);
-        const int pos = b.idx[at];
-        key = b.key[at];
-        id = pos >= 0 && pos < a.N ? a.ids[pos] : INT_MAX;   // (always inside: the test keeps a broken invariant from reading)
-      }
-      a.ws_key[out + j] = key;
-      a.ws_idx[out + j] = id;
-    }
-  }
+  const unsigned char* qrow = smem + (size_t)r * t.pitch;
+  buffered_steps(t, cut.begin, cut.end, occ, k, [&](int64_t base) {
+    // a tile row past the cut reads row min(.., N - 1) instead (its scores are never looked at)
+    const int64_t grow = min(base + r, (int64_t)a.N - 1);
+    return score_tile(a.g + grow * a.ld_g, qrow, h, groups, tail);
+  });
+  emit_pairs(t, occ, k, a.ws_key, a.ws_idx, out, a.ids, a.N);      // the original row in place of the position
 }
 
 __global__ void __launch_bounds__(kThreads) embed_lists_grouped_pass2(SelectArgs a) { select_pass2(a); }
@@ -266,30 +164,10 @@ int64_t tiles_bound(int B, int L, int nprobe) {
   return by_pairs < by_lists ? by_pairs : by_lists;
 }
 
-// validates the shape of a call and resolves parts = 0; returns 0 or TFIMM_EINVAL with the message set
+// the shape of a call as embed_search_lists takes it, and the buffers of a query tile in LDS
 int resolve(int B, int N, int E, int L, int nprobe, int k, int* parts) {
-  if (E < TFIMM_EMBED_MIN_E || E > TFIMM_EMBED_MAX_E || E % 16 != 0)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: E=%d, must be a multiple of 16 in [%d, TFIMM_EMBED_MAX_E = %d]", E,
-               TFIMM_EMBED_MIN_E, TFIMM_EMBED_MAX_E);
-  if (N < 1) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: N=%d, must be in [1, 2^31)", N);
-  if (L < 1 || L > TFIMM_CLUSTER_MAX_C)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: L=%d, must be in [1, TFIMM_CLUSTER_MAX_C = %d]", L, TFIMM_CLUSTER_MAX_C);
-  if (nprobe < 1 || nprobe > TFIMM_EMBED_LISTS_MAX_PROBE)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: nprobe=%d, must be in [1, TFIMM_EMBED_LISTS_MAX_PROBE = %d]", nprobe,
-               TFIMM_EMBED_LISTS_MAX_PROBE);
-  if (k < 1 || k > TFIMM_EMBED_WIDE_MAX_K)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: k=%d, must be in [1, TFIMM_EMBED_WIDE_MAX_K = %d]", k, TFIMM_EMBED_WIDE_MAX_K);
-  if (*parts < 0 || *parts > kMaxParts)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: parts=%d, must be 0 (the library chooses) or in [1, %d]", *parts, kMaxParts);
-  if (*parts == 0) *parts = 1;
-  if (B < 0 || B > kMaxB) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: B=%d, must be in [0, %d]", B, kMaxB);
-  const int most = tfimm_hip_embed_search_wide_max_k(E);
-  if (k > most)
-    TFIMM_FAIL(TFIMM_EINVAL,
-               "embed_search_lists_grouped: E=%d with k=%d: 32 buffers of k + %d pairs do not fit %d KiB of LDS next to the query "
-               "tile; tfimm_hip_embed_search_wide_max_k(%d) = %d",
-               E, k, kStepRows, kLdsBudget / 1024, E, most);
-  return 0;
+  TFIMM_EMBED_TRY(resolve_lists(kFn, B, N, E, L, nprobe, k, parts, ""));
+  return check_tile_fit(kFn, E, k);
 }
 
 // the pair arrays of tfimm_hip_embed_search_lists, then count [L], first [L + 1], rank [P], tile_list [T], members [T][32]
@@ -311,8 +189,7 @@ extern "C" int64_t tfimm_hip_embed_search_lists_grouped_tiles(int B, int L, int 
 }
 
 extern "C" int64_t tfimm_hip_embed_search_lists_grouped_workspace(int B, int N, int E, int L, int nprobe, int k, int parts) {
-  const int rc = resolve(B, N, E, L, nprobe, k, &parts);
-  if (rc) return rc;
+  TFIMM_EMBED_TRY(resolve(B, N, E, L, nprobe, k, &parts));
   return workspace_need(B, L, nprobe, k, parts);
 }
 
@@ -320,33 +197,12 @@ extern "C" int tfimm_hip_embed_search_lists_grouped(const float* q, int64_t ld_q
                                                     const int32_t* ids, const int32_t* offsets, int L, const int32_t* probes,
                                                     int64_t ld_p, int nprobe, int k, int parts, float* scores, int32_t* indices,
                                                     void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!q) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: q is null");
-  if (!g) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: g is null");
-  if (!ids) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: ids is null");
-  if (!offsets) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: offsets is null");
-  if (!probes) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: probes is null");
-  if (!scores) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: scores is null");
-  if (!indices) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: indices is null");
-  if (!workspace) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: workspace is null");
-  if ((uintptr_t)g & 15) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: g must be 16-byte aligned");
-  if (((uintptr_t)q | (uintptr_t)ids | (uintptr_t)offsets | (uintptr_t)probes | (uintptr_t)scores | (uintptr_t)indices |
-       (uintptr_t)workspace) & 3)
-    TFIMM_FAIL(TFIMM_EINVAL,
-               "embed_search_lists_grouped: q, ids, offsets, probes, scores, indices and workspace hold 4-byte elements and must be "
-               "4-byte aligned");
-  const int rc = resolve(B, N, E, L, nprobe, k, &parts);
-  if (rc) return rc;
-  if (ld_q < E) TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: ld_q=%lld is smaller than E=%d", (long long)ld_q, E);
-  if (ld_g < E || ld_g % 8 != 0)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: ld_g=%lld, must be a multiple of 8 elements and at least E=%d", (long long)ld_g,
-               E);
-  if (ld_p < nprobe)
-    TFIMM_FAIL(TFIMM_EINVAL, "embed_search_lists_grouped: ld_p=%lld is smaller than nprobe=%d", (long long)ld_p, nprobe);
-  const int64_t need = workspace_need(B, L, nprobe, k, parts);
-  if (workspace_bytes < need)
-    TFIMM_FAIL(TFIMM_EINVAL,
-               "embed_search_lists_grouped: workspace_bytes=%lld, tfimm_hip_embed_search_lists_grouped_workspace asks for %lld",
-               (long long)workspace_bytes, (long long)need);
+  TFIMM_EMBED_TRY(check_lists_pointers(kFn, q, g, ids, offsets, probes, scores, indices, workspace));
+  TFIMM_EMBED_TRY(resolve(B, N, E, L, nprobe, k, &parts));
+  TFIMM_EMBED_TRY(check_ld_q(kFn, ld_q, E));
+  TFIMM_EMBED_TRY(check_ld_g(kFn, ld_g, E));
+  TFIMM_EMBED_TRY(check_ld_p(kFn, ld_p, nprobe));
+  TFIMM_EMBED_TRY(check_workspace(kFn, workspace_bytes, workspace_need(B, L, nprobe, k, parts)));
   if (B == 0) return 0;
 
   static tfimm_once_t ready;

@@ -1,5 +1,8 @@
-// The score loop shared by the first passes of tfimm_hip_embed_search (embed.hip) and tfimm_hip_embed_search_wide
-// (embed_wide.hip): the query tile rounded to bf16 in LDS, and one 32 x 32 tile of float32 scores of 32 gallery rows against it.
+// The score loop shared by the five gallery searches: the query tile rounded to bf16 in LDS, and one 32 x 32 tile of float32
+// scores of 32 gallery rows against it.  Its users: the first passes of tfimm_hip_embed_search (embed.hip),
+// tfimm_hip_embed_search_wide (embed_wide.hip), tfimm_hip_embed_search_lists (embed_lists.hip, one query in all 32 columns) and
+// tfimm_hip_embed_search_lists_grouped (embed_lists_grouped.hip, the tile gathered through its members), and the rerank of
+// tfimm_hip_embed_search_coarse (embed_coarse.hip), whose fp8 scan keeps the tile's shape and lane map.
 //
 // The query tile: 32 rows of E bf16 values, row pitch 2 E + 16 bytes (pitch / 16 is odd, so the 16 lanes of a ds_read_b128
 // pass fall on 16 distinct 16-byte bank groups).  The 16 bytes behind a row's values are never read by the score loop.
@@ -8,7 +11,7 @@
 // holds A[row r][k = 8h .. 8h+7], 16 contiguous bytes of gallery row r.  k is permuted identically on both operands so that
 // within 64 columns lane (r, h) owns columns 32h .. 32h+31: it reads 64 contiguous bytes of its row per four MFMA steps (the
 // < 64 columns behind the last full group use the plain map).  The MFMA steps run in ascending column order from a zero
-// accumulator, so a score is a function of its query and its gallery row alone -- the same bits from either entry point.  The
+// accumulator, so a score is a function of its query and its gallery row alone -- the same bits from every entry point.  The
 // result has the query on the lane (column = lane & 31) and 16 gallery rows in the registers: register i of lane (r, h) is
 // gallery row (i & 3) + 8 (i >> 2) + 4 h of the tile.
 #pragma once

@@ -198,6 +198,32 @@ def test_padded_rows_are_never_read():
     check_exact(q, g, 5, 20, 0, pad_q=1, pad_g=24, pad_c=48)
 
 
+def test_ascending_keys_force_a_prune_on_every_other_step():
+    """Row n is (8 + n % 8) * 2^(n // 8 - 60) in column 0 and zero elsewhere: every row quantises exactly, so for the query +e0
+    the coarse keys rise strictly with the row -- every row of the scan beats the threshold, each step fills 128 slots of every
+    buffer, and a prune is due on every other step -- and for -e0 they fall strictly: nothing is appended after the first
+    prune.  The result is the rule's, and the rule's is known: the last rows downwards, the first rows upwards."""
+    N, E = 896, 16
+    n = np.arange(N)
+    g = np.zeros((N, E), f32)
+    g[:, 0] = np.ldexp((8 + n % 8).astype(f32), n // 8 - 60)
+    q = np.zeros((2, E), f32)
+    q[0, 0], q[1, 0] = 1, -1
+    codes, exps = cr.quantize_rows(g)
+    assert (int(exps.min()), int(exps.max())) == (-65, 47)
+    assert np.array_equal(np.ldexp(cr.e4m3_decode(codes), exps.astype(np.int64)[:, None]), g.astype(np.float64))
+    keys = cr.keys64(q, g)[0]
+    assert (np.diff(keys[0]) > 0).all() and (np.diff(keys[1]) < 0).all()
+    d = Device(q, g)
+    for c, k in ((64, 64), (256, 256), (256, 5)):
+        want_idx, want_sc, _ = cr.search_coarse(q, g, k, c)
+        assert want_idx.tolist() == [list(range(N - 1, N - 1 - k, -1)), list(range(k))]
+        for chunk in (896, 0):
+            idx, sc = d.search(k, c, chunk)
+            assert np.array_equal(idx, want_idx), (c, k, chunk, idx[idx != want_idx][:8], want_idx[idx != want_idx][:8])
+            assert np.array_equal(er.bits(sc), er.bits(want_sc)), (c, k, chunk)
+
+
 N_STRESS = 40000
 
 
