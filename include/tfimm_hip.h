@@ -1252,6 +1252,42 @@ TFIMM_API int tfimm_hip_embed_search_lists_grouped(const float* q, int64_t ld_q,
                                                    int64_t ld_p, int nprobe, int k, int parts, float* scores, int32_t* indices,
                                                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* tfimm_hip_matches_merge (csrc/embed_merge.hip; the CPU restatement of the rule is tests/live_ref.py::merge): the
+ * k best of S SETS of matches per query -- what the searches of two galleries, of the shards of one, or of a GalleryIndex and of
+ * the rows added behind it leave -- joined on the device.  Set s holds, for each of the B queries, k_s (index, score) entries at
+ * pitch ld: `sets` is a HOST array that is read during the call; its contents travel as kernel arguments, so nothing of it is
+ * referenced after the call returns.
+ *   Entry j of set s in row b is a CANDIDATE iff indices[b][j] >= 0.  Its row is indices[b][j] + base_s (the caller keeps it
+ *   below 2^31), its key the order-preserving key of its score (csrc/topk_select.h: every NaN ranks above +inf, the two zeros
+ *   are equal).  scores / indices [b][0:k] receive the k best candidates of all sets, key descending, equal keys by ascending
+ *   row; a score is written as the float its key stands for -- the bits every search here writes pass through unchanged, -0.0
+ *   becomes +0.0 and any NaN the one quiet NaN --; the slots behind the last candidate hold index -1 and score -inf.  A
+ *   candidate with score -inf is a candidate and comes before that fill.
+ * Preconditions, documented and NOT checked: every set's row is as the searches leave it -- the valid entries first, in the
+ * order above, -1 entries behind them --, and the rows of one query are pairwise distinct after `base`.  Where they do not hold
+ * the result is unspecified; even then nothing outside scores / indices [B][k] is written.  Columns >= k_s of a set and columns
+ * >= k of the outputs are never touched.  Outputs must not alias inputs.
+ * One launch on `stream`, no workspace: one wave per query, four queries per workgroup, a grid-stride loop over the queries
+ * (B is no grid dimension); the first min(k_s, k) entries of every set stand in LDS as 64-bit words, 8 * sum_s min(k_s, k) bytes
+ * per wave (at most 64 KiB per workgroup), and an entry's place in the result is its position in its own set plus, per other
+ * set, the entries that beat it: a binary search.  The result is a function of the candidate set alone: bit-reproducible,
+ * independent of B and of which queries share a call; no atomics, no scratch memory, no allocation, capturable; offsets are
+ * 64-bit.
+ * TFIMM_EINVAL before any launch, with a message naming the argument: sets, scores or indices NULL; a set's scores or indices
+ * NULL ("sets[1].indices is null"); any of those pointers not 4-byte aligned; S outside [1, TFIMM_MERGE_MAX_SETS]; k or a set's k
+ * outside [1, TFIMM_EMBED_WIDE_MAX_K]; a set's ld < its k; ld_out < k; a negative base; B outside [0, TFIMM_EMBED_MAX_B].
+ * B == 0 returns 0 and launches nothing. */
+#define TFIMM_MERGE_MAX_SETS 8
+typedef struct tfimm_match_set {
+  const float*   scores;   /* [B][ld] */
+  const int32_t* indices;  /* [B][ld] */
+  int64_t ld;              /* >= k    */
+  int32_t k;               /* columns of this set, 1 .. TFIMM_EMBED_WIDE_MAX_K */
+  int32_t base;            /* >= 0: added to every valid index */
+} tfimm_match_set;         /* 32 bytes */
+TFIMM_API int tfimm_hip_matches_merge(const tfimm_match_set* sets, int S, int B, int k, float* scores, int32_t* indices,
+                                      int64_t ld_out, void* stream);
+
 /* =======================================================================================
  * KNN END (csrc/knn.hip; the CPU restatement of the rule is tests/knn_ref.py): the matches of a gallery
  * search turned into classes through a label per gallery row, in one launch behind tfimm_hip_embed_search.

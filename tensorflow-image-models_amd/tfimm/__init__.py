@@ -7,7 +7,7 @@ Drop-in for the inference path of martinsbruveris/tensorflow-image-models:
 from . import architectures, layers  # noqa: F401
 from .models.embedding_model import EmbeddingModel  # noqa: F401
 from .models.factory import create_model, create_preprocessing  # noqa: F401
-from .models.gallery import Assigned, Clusters, Gallery, Matches, Votes  # noqa: F401
+from .models.gallery import Assigned, Clusters, Gallery, Matches, Votes, merge_matches  # noqa: F401
 from .models.gallery_index import GalleryIndex  # noqa: F401
 from .models.meter import Meter, MeterResult, MeterState, Scores, score  # noqa: F401
 from .models.model import Tensor, TopK  # noqa: F401

@@ -215,6 +215,11 @@ class ResizeBatchSizes(C.Structure):
                 ("max_taps", C.c_int32), ("lds_floats", C.c_int32), ("bad_image", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MatchSet(C.Structure):
+    """tfimm_match_set: one set of matches for tfimm_hip_matches_merge (csrc/embed_merge.hip) -- 32 bytes"""
+    _fields_ = [("scores", C.c_void_p), ("indices", C.c_void_p), ("ld", C.c_int64), ("k", C.c_int32), ("base", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tfimm_hip.h
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -301,6 +306,8 @@ SYMBOLS = {
     "tfimm_hip_embed_search_lists_grouped_workspace": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "tfimm_hip_embed_search_lists_grouped": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64,
                                                   _vp]),
+    # the join of up to MERGE_MAX_SETS sets of matches (csrc/embed_merge.hip): sets, S, B, k, scores, indices, ld_out
+    "tfimm_hip_matches_merge": (_i, [C.POINTER(MatchSet), _i, _i, _i, _vp, _vp, _i64, _vp]),
     # the kNN end (csrc/knn.hip): indices, scores, ld, B, k, glabels, N, exclude, inv_temperature, then
     # reduce, top, classes, values, counts, total | nb_classes, labels, loss, rank, pred, prob, state, per_class, confusion
     "tfimm_hip_knn_vote": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -452,6 +459,7 @@ EMBED_LISTS_MAX_PARTS = 64        # ... and cuts of a list, one workgroup each
 EMBED_LISTS_MAX_B = 65535         # ... and queries per call: one grid dimension
 EMBED_LISTS_GROUPED_TILE = 32     # tfimm_hip_embed_search_lists_grouped: queries of one list per workgroup of the first pass;
                                   # its k obeys tfimm_hip_embed_search_wide_max_k(E) as well
+MERGE_MAX_SETS = 8                # tfimm_hip_matches_merge: sets of matches per call
 # include/tfimm_hip.h: the domain of tfimm_hip_knn_vote / tfimm_hip_knn_score (one lane per candidate and per slot of the list)
 KNN_MAX_K, KNN_MAX_TOP, KNN_SUM, KNN_MAX = EMBED_MAX_K, 64, 0, 1
 # include/tfimm_hip.h: centroids per tfimm_hip_cluster_assign; entries per run of tfimm_hip_segment_mean's summation rule

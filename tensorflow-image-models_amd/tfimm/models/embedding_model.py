@@ -191,6 +191,15 @@ class EmbeddingModel(Model):
         index._args(k, nprobe)
         return index.search(self._embeddings_for(x, index), k, nprobe)
 
+    def search_live(self, x, index, k: int = 5, nprobe: int = 8):
+        """``index.search_live(model(x), k, nprobe)`` for a ``tfimm.GalleryIndex`` whose gallery has grown: the probed lists
+        and every row added since the build; ``Matches(indices, scores)``, each (B, k).  Every argument is
+        checked before the forward pass runs."""
+        if index.dim != self.embed_dim:
+            raise ValueError(f"{self.name}: embeddings have {self.embed_dim} columns, the index holds rows of {index.dim}")
+        index._live_args(k, nprobe, "single", "GalleryIndex.search_live")
+        return index.search_live(self._embeddings_for(x, index), k, nprobe)
+
     def _embeddings_for(self, x, gallery):
         emb = self(x)
         if len(emb.shape) != 2:

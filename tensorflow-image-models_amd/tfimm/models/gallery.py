@@ -58,6 +58,91 @@ def _row_labels(labels, n, what):
     return upload
 
 
+def _merge_launch(sets, k: int):
+    """tfimm_hip_matches_merge on the current stream: ``sets`` is 1 to 8 triples (int32 indices (B, k_s), float32 scores
+    (B, k_s), base), contiguous torch tensors on one device, B >= 1 -> (indices, scores) torch tensors (B, k); no
+    synchronisation"""
+    import torch
+    from ..engine import ffi
+    B, dev = int(sets[0][0].shape[0]), sets[0][0].device
+    indices = torch.empty((B, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, k), dtype=torch.float32, device=dev)
+    arr = (ffi.MatchSet * len(sets))()
+    for rec, (i, s, base) in zip(arr, sets):
+        rec.scores, rec.indices, rec.ld, rec.k, rec.base = s.data_ptr(), i.data_ptr(), int(i.shape[1]), int(i.shape[1]), int(base)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ffi.check(ffi.lib.tfimm_hip_matches_merge(arr, len(sets), B, int(k), scores.data_ptr(), indices.data_ptr(), int(k), st),
+              "tfimm_hip_matches_merge")
+    return indices, scores
+
+
+def merge_matches(parts, bases=None, k=None) -> Matches:
+    """The ``k`` best of several ``Matches`` per query, joined on the device (tfimm_hip_matches_merge, csrc/embed_merge.hip;
+    DESIGN.md 3.30): ``parts`` is a sequence of 1 to 8 ``Matches`` on one device with the same number of queries -- the
+    results of the shards of a gallery, of several galleries, of a second device after a copy --, ``bases`` the row offset of
+    each part in the common numbering (integers >= 0; default all 0), ``k`` the width of the result (default: the widest part;
+    ``1 <= k <= 256``).  Entries with index -1 are no candidates; the result is ordered as ``Gallery.search`` orders --
+    score descending, equal scores by ascending row (after the base) --, scores keep their bits, and the slots behind the last
+    candidate hold -1 / -inf.  The parts must be what the searches return -- valid entries first, in that order -- and the
+    rows of a query distinct across the parts; otherwise the result is unspecified.  One launch on the current stream,
+    nothing goes to the host; every ``ValueError`` comes before any device work."""
+    import torch
+    from ..engine import ffi
+    what = "merge_matches"
+    if isinstance(parts, Matches) or not isinstance(parts, (list, tuple)):
+        raise ValueError(f"{what}: parts must be a sequence of Matches, got {type(parts).__name__}")
+    if not 1 <= len(parts) <= ffi.MERGE_MAX_SETS:
+        raise ValueError(f"{what}: parts: {len(parts)} Matches, must be 1 to TFIMM_MERGE_MAX_SETS = {ffi.MERGE_MAX_SETS}")
+    if bases is None:
+        bases = [0] * len(parts)
+    try:
+        bases = list(bases)
+    except TypeError:
+        raise ValueError(f"{what}: bases must be a sequence of integers, got {bases!r}") from None
+    if len(bases) != len(parts):
+        raise ValueError(f"{what}: bases: {len(bases)} offsets for {len(parts)} parts")
+    for n, base in enumerate(bases):
+        if not _is_int(base) or base < 0 or base >= 2 ** 31:
+            raise ValueError(f"{what}: bases[{n}] = {base!r}, must be an integer in [0, 2^31)")
+    sets = []
+    for n, m in enumerate(parts):
+        try:
+            i, s = (x.torch() if isinstance(x, Tensor) else x for x in m)
+            ok = isinstance(i, torch.Tensor) and isinstance(s, torch.Tensor)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what}: parts[{n}] must be the Matches(indices, scores) of a search, got {type(m).__name__}")
+        if i.dtype != torch.int32 or s.dtype != torch.float32 or i.ndim != 2 or i.shape != s.shape:
+            raise ValueError(f"{what}: parts[{n}]: expected int32 indices and float32 scores of one shape (B, k), got {i.dtype} "
+                             f"{tuple(i.shape)} and {s.dtype} {tuple(s.shape)}")
+        if not 1 <= i.shape[1] <= ffi.EMBED_WIDE_MAX_K:
+            raise ValueError(f"{what}: parts[{n}] with k = {i.shape[1]}, must be in [1, TFIMM_EMBED_WIDE_MAX_K = {ffi.EMBED_WIDE_MAX_K}]")
+        sets.append((i, s, int(bases[n])))
+    B = int(sets[0][0].shape[0])
+    for n, (i, _, _) in enumerate(sets):
+        if int(i.shape[0]) != B:
+            raise ValueError(f"{what}: parts[{n}] holds {int(i.shape[0])} queries, parts[0] holds B = {B}")
+    if B > ffi.EMBED_MAX_B:
+        raise ValueError(f"{what}: {B} queries, at most TFIMM_EMBED_MAX_B = {ffi.EMBED_MAX_B} per call")
+    if k is None:
+        k = max(int(i.shape[1]) for i, _, _ in sets)
+    if not _is_int(k):
+        raise ValueError(f"{what}: k must be an integer, got {k!r}")
+    if k < 1 or k > ffi.EMBED_WIDE_MAX_K:
+        raise ValueError(f"{what}: k = {k}, must be in [1, TFIMM_EMBED_WIDE_MAX_K = {ffi.EMBED_WIDE_MAX_K}]")
+    dev = sets[0][0].device
+    for n, (i, s, _) in enumerate(sets):
+        if not (i.is_cuda and s.is_cuda) or i.device != dev or s.device != dev:
+            raise ValueError(f"{what}: parts[{n}] must be on the device, and all parts on one (what Gallery.search returns)")
+    k = int(k)
+    if B == 0:
+        return Matches(Tensor(torch.empty((0, k), dtype=torch.int32, device=dev)), Tensor(torch.empty((0, k), dtype=torch.float32, device=dev)))
+    with torch.cuda.device(dev):
+        indices, scores = _merge_launch([(i.contiguous(), s.contiguous(), b) for i, s, b in sets], k)
+    return Matches(Tensor(indices), Tensor(scores))
+
+
 class Gallery:
     """``Gallery(dim, capacity=0)``: a growing (N, dim) matrix of bf16 rows in device memory with a 16-byte-aligned row
     pitch.  ``add`` appends float32 rows (rounded to nearest even), ``search`` returns for every query the ``k`` rows with
@@ -285,6 +370,82 @@ class Gallery:
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         ffi.check(getattr(ffi.lib, name)(t.data_ptr(), self.dim, B, self._buf.data_ptr(), self.pitch, self._n, self.dim, k,
                                          int(chunk), scores.data_ptr(), indices.data_ptr(), work.data_ptr(), work.numel(), st), name)
+        return Matches(Tensor(indices), Tensor(scores))
+
+    # -- the exact search of a row range, and the join of matches (csrc/embed_merge.hip) ---------------------------
+    def _range_args(self, k, start, stop, method, what="Gallery.search_range"):
+        """every ``ValueError`` of ``search_range`` about ``k``, the range and ``method``; returns (start, rows, the ``k`` the
+        search runs for -- ``min(k, rows)`` --, its path; None for an empty range).  No device work."""
+        from ..engine import ffi
+        if not _is_int(k):
+            raise ValueError(f"{what}: k must be an integer, got {k!r}")
+        if method not in _METHODS:
+            raise ValueError(f"{what}: method = {method!r}, must be one of {', '.join(map(repr, _METHODS))}")
+        if stop is None:
+            stop = self._n
+        if not _is_int(start) or not _is_int(stop):
+            raise ValueError(f"{what}: start and stop must be integers (stop may be None: len), got {start!r} and {stop!r}")
+        if not 0 <= start <= stop <= self._n:
+            raise ValueError(f"{what}: rows [{start}, {stop}): 0 <= start <= stop <= len = {self._n} must hold")
+        if k < 1 or k > ffi.EMBED_WIDE_MAX_K:
+            raise ValueError(f"{what}: k = {k}, must be in [1, TFIMM_EMBED_WIDE_MAX_K = {ffi.EMBED_WIDE_MAX_K}] (it may exceed the "
+                             f"rows of the range: the slots behind them hold -1 / -inf)")
+        rows = int(stop) - int(start)
+        ks = min(int(k), rows)
+        if not rows:
+            return int(start), 0, 0, None
+        try:
+            path = self._route(ks, method)                     # ks <= rows <= len: the width limits of the route remain
+        except ValueError as e:
+            raise ValueError(str(e).replace("Gallery.search", what)) from None
+        return int(start), rows, ks, path
+
+    def _range_launch(self, t, ks: int, start: int, rows: int, path: str):
+        """the exact search of device queries ``t`` float32 (B, dim), B >= 1, among rows [start, start + rows) for ``ks <=
+        rows`` neighbours by ``path`` -> (indices, scores) torch tensors (B, ks); the indices count from ``start``.  The
+        existing entry points on the gallery's buffer at a row offset: ``pitch`` is a multiple of 8 elements, so the rows stay
+        16-byte aligned.  Two launches on the current stream."""
+        import torch
+        from ..engine import ffi
+        B = int(t.shape[0])
+        scores = torch.empty((B, ks), dtype=torch.float32, device=t.device)
+        indices = torch.empty((B, ks), dtype=torch.int32, device=t.device)
+        name = "tfimm_hip_embed_search" if path == "list" else "tfimm_hip_embed_search_wide"
+        need = getattr(ffi.lib, name + "_workspace")(B, rows, self.dim, ks, 0)
+        if need < 0:
+            ffi.check(int(need), name + "_workspace")
+        # an entry of its own: a whole-gallery search that outgrows its workspace replaces that tensor, and a captured graph of
+        # this search must not hold the address of a workspace another search can free
+        work = self._work.get((B, ks, path, "range"))
+        if work is None or work.numel() < need:
+            work = self._work[(B, ks, path, "range")] = torch.empty(int(need), dtype=torch.uint8, device=t.device)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(getattr(ffi.lib, name)(t.data_ptr(), int(t.stride(0)), B, self._buf.data_ptr() + 2 * start * self.pitch, self.pitch,
+                                         rows, self.dim, ks, 0, scores.data_ptr(), indices.data_ptr(), work.data_ptr(),
+                                         work.numel(), st), name)
+        return indices, scores
+
+    def search_range(self, q, k: int = 5, start: int = 0, stop=None, method: str = "auto") -> Matches:
+        """``search`` among the rows ``[start, stop)`` only (``stop=None``: ``len``): ``Matches`` whose indices are the
+        gallery's own numbers, whose scores have the bits ``search`` gives for those rows, in ``search``'s order.  ``k <= 256``
+        may exceed the rows of the range: the search runs for ``min(k, rows)`` and the slots behind hold index -1 and score
+        -inf; an empty range gives nothing else and launches no search.  ``method`` and the width limits are those of
+        ``search_with``, applied to ``min(k, rows)``.  The search's two launches on the gallery's buffer at a row offset, then
+        tfimm_hip_matches_merge with one set, which adds ``start`` and fills; nothing goes to the host.  With ``merge_matches``
+        this searches a gallery in pieces; ``GalleryIndex.search_live`` searches the rows an index does not hold with it."""
+        import torch
+        from ..engine import ffi
+        what = "Gallery.search_range"
+        start, rows, ks, path = self._range_args(k, start, stop, method, what)
+        t = self._upload_rows(self._check_rows(q, "search_range")).contiguous()
+        B, k = int(t.shape[0]), int(k)
+        if B > ffi.EMBED_MAX_B:
+            raise ValueError(f"{what}: {B} queries, at most TFIMM_EMBED_MAX_B = {ffi.EMBED_MAX_B} per call")
+        if B == 0 or not rows:
+            return Matches(Tensor(torch.full((B, k), -1, dtype=torch.int32, device=t.device)),
+                           Tensor(torch.full((B, k), float("-inf"), dtype=torch.float32, device=t.device)))
+        i, s = self._range_launch(t, ks, start, rows, path)
+        indices, scores = _merge_launch([(i, s, start)], k)
         return Matches(Tensor(indices), Tensor(scores))
 
     # -- the coarse-to-fine search: fp8 scan, exact bf16 rerank (csrc/embed_coarse.hip; DESIGN.md 3.27) ---------------------------

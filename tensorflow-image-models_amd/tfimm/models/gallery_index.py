@@ -3,7 +3,10 @@ that scores only the lists a query probes (tfimm_hip_embed_search_lists, csrc/em
 search path of ``Gallery`` reads the whole gallery; this one reads ``nprobe`` of ``n_lists`` lists, and pays with recall: a row
 whose list is not probed is not found.  The rule is restated on the CPU in tests/index_ref.py.  ``search_with`` chooses the
 first pass -- one query per workgroup, or the queries of a list grouped into MFMA tiles (tfimm_hip_embed_search_lists_grouped,
-csrc/embed_lists_grouped.hip): the same bits --, and ``neighbours`` is the kNN graph of the indexed rows."""
+csrc/embed_lists_grouped.hip): the same bits --, and ``neighbours`` is the kNN graph of the indexed rows.  The
+index follows a gallery that grows: ``search_live`` / ``classify_live`` search the probed lists AND every row
+added since the build -- the exact search of that row range, joined by tfimm_hip_matches_merge (csrc/embed_merge.hip; the rule
+is tests/live_ref.py) --, and ``absorb`` takes those rows into the lists without a k-means run."""
 import ctypes as C
 import math
 
@@ -23,19 +26,26 @@ class GalleryIndex:
     """What ``gallery.build_index(...)`` returns: a SNAPSHOT of the gallery's first ``size`` rows as ``n_lists`` inverted
     lists.  The index owns a copy of the bf16 rows in list order (the gallery's memory, once more), the original row of every
     position (``ids``, ascending inside a list) and the lists' ``offsets``; ``centroids`` is the labelled ``Gallery`` of
-    ``kmeans`` and ``counts`` the rows per list.  Rows added to the gallery later are not seen until a new build: ``stale``
-    says that there are some.  ``Gallery.search``, ``classify`` and ``evaluate`` never come here."""
+    ``kmeans`` and ``counts`` the rows per list.  Rows added to the gallery later are not seen by ``search``, ``search_with``,
+    ``classify`` and ``neighbours``: ``stale`` says that there are some, ``fresh`` how many.  ``search_live`` and
+    ``classify_live`` see them -- they search the rows behind the snapshot exactly and merge --, ``absorb`` moves them into
+    the lists (the centroids stay), and a new ``build_index`` clusters anew.  ``Gallery.search``, ``classify`` and
+    ``evaluate`` never come here."""
 
     def __init__(self, gallery, clusters):
-        import torch
         cen = clusters.centroids
-        n, nl = len(gallery), len(cen)
         assignment = clusters.assignment.torch() if isinstance(clusters.assignment, Tensor) else clusters.assignment
         self._gallery = gallery
         self.dim, self.pitch = gallery.dim, gallery.pitch
-        self.size = n
-        self.n_lists = nl
+        self.n_lists = len(cen)
         self.centroids = cen
+        self._lay(assignment)
+
+    def _lay(self, assignment):
+        """the lists of the gallery's rows as ``assignment`` (len,) groups them: what the constructor and ``absorb`` share"""
+        import torch
+        gallery, n, nl = self._gallery, len(self._gallery), self.n_lists
+        self.size = n
         # plumbing, as Gallery._segment_means does it: a stable sort of the lists (rows ascend inside a list) and searchsorted
         ordered, order = torch.sort(assignment, stable=True)
         dev = ordered.device
@@ -53,6 +63,12 @@ class GalleryIndex:
     def stale(self) -> bool:
         """whether the gallery has grown since the build: its later rows are not searched"""
         return len(self._gallery) != self.size
+
+    @property
+    def fresh(self) -> int:
+        """the rows the gallery holds and the snapshot does not: ``len(gallery) - size``; ``search_live`` searches them
+        exactly, ``absorb`` takes them into the lists"""
+        return len(self._gallery) - self.size
 
     def lists(self):
         """``(ids, offsets)`` as numpy int32 arrays, (size,) and (n_lists + 1,): list ``l`` holds the original rows
@@ -190,7 +206,8 @@ class GalleryIndex:
         return Matches(Tensor(indices), Tensor(scores))
 
     def neighbours(self, k: int = 20, nprobe: int = 8, batch: int = 8192, method: str = "grouped") -> Matches:
-        """The kNN graph of the indexed rows: ``Matches`` of shape (size, k), row ``i`` the ``k`` nearest OTHER indexed rows of
+        """The kNN graph of the indexed rows -- the SNAPSHOT: fresh rows are neither queries nor neighbours until ``absorb`` --:
+        ``Matches`` of shape (size, k), row ``i`` the ``k`` nearest OTHER indexed rows of
         original row ``i`` among the lists it probes, in ``search``'s order (-1 / -inf behind short results).  The rows are
         their own queries (exact from bf16) and go in LIST order, ``batch`` at a time: a batch then names few lists and fills
         its tiles.  Each batch is searched for ``k + 1`` -- which obeys the limits of ``search_with`` --; of every result row
@@ -250,6 +267,144 @@ class GalleryIndex:
         up_ex = g._exclude(exclude, int(t.shape[0]), what)
         m = self.search(q, int(k) + extra, nprobe)
         return g._launch_vote(m.indices.torch(), m.scores.torch(), up_ex, inv_t, red, int(top))
+
+    # -- the index of a gallery that grows (csrc/embed_merge.hip) ---------------------------------------------------
+    def _live_args(self, k, nprobe, method, what):
+        """every ``ValueError`` of ``search_live`` about ``k``, ``nprobe`` and ``method``, from both halves -- the index's
+        limits are ``search_with``'s for that method, the exact search of the fresh rows has its own width limits --; returns
+        (parts, the tail's arguments as ``Gallery._range_args`` gives them; None without fresh rows).  No device work."""
+        try:
+            parts = self._method_args(k, nprobe, 0, method, what)
+        except ValueError as e:
+            if "with method=" not in str(e):
+                raise
+            raise ValueError(str(e).replace(f"{what}: ", f"{what}: the index half refused: ", 1)) from None
+        if not self.fresh:
+            return parts, None
+        try:
+            tail = self._gallery._range_args(k, self.size, len(self._gallery), "auto", what)
+        except ValueError as e:
+            raise ValueError(str(e).replace(f"{what}: ", f"{what}: the exact half (the {self.fresh} fresh rows) refused: ", 1)) from None
+        return parts, tail
+
+    def _live(self, t, k, nprobe, parts, method, tail):
+        """the device part of ``search_live`` for device queries ``t``, B >= 1 -> (indices, scores) torch tensors"""
+        from .gallery import _merge_launch
+        probes = self.centroids.search(t, nprobe).indices.torch()
+        indices, scores = self._launch(t, probes, k, nprobe, parts, method)
+        if tail is None:
+            return indices, scores
+        start, rows, ks, path = tail
+        ti, ts = self._gallery._range_launch(t, ks, start, rows, path)
+        return _merge_launch([(indices, scores, 0), (ti, ts, start)], k)
+
+    def search_live(self, q, k: int = 5, nprobe: int = 8, method: str = "single") -> Matches:
+        """``search`` for a gallery that has grown: per query the ``k`` best rows among the rows of the ``nprobe`` probed lists
+        AND every fresh row (the rows ``size .. len(gallery)`` the snapshot does not hold) -- ``search``'s order, row
+        numbers and score bits; the rule is tests/live_ref.py::search_live.  A fresh row is always found: the rows behind the
+        snapshot are searched exactly (``gallery.search_range(q, k, size, len)``) and tfimm_hip_matches_merge joins the two
+        results, all on the current stream, nothing goes to the host.  Without fresh rows this is ``search_with(q, k,
+        nprobe, 0, method)``, launch for launch.  With ``nprobe == n_lists`` the result is ``gallery.search(q, k)``, bit for
+        bit.  ``method`` is the first pass of ``search_with``; ``k`` must be acceptable to both halves -- the index's limits
+        for that method and the exact search's width limits -- and the ``ValueError`` says which half refused.  The tail
+        costs a scan of the fresh rows per call: ``absorb`` when they have become many."""
+        import torch
+        what = "GalleryIndex.search_live"
+        parts, tail = self._live_args(k, nprobe, method, what)
+        t = self._gallery._upload_rows(self._queries(q, what)).contiguous()
+        B, k, nprobe = int(t.shape[0]), int(k), int(nprobe)
+        if B == 0:
+            return Matches(Tensor(torch.empty((0, k), dtype=torch.int32, device=t.device)),
+                           Tensor(torch.empty((0, k), dtype=torch.float32, device=t.device)))
+        indices, scores = self._live(t, k, nprobe, parts, method, tail)
+        return Matches(Tensor(indices), Tensor(scores))
+
+    def classify_live(self, q, k: int = 20, nprobe: int = 8, temperature=0.07, top: int = 5, reduce: str = "sum", exclude=None) -> Votes:
+        """``classify`` over ``search_live``'s matches: enrol, then recognise -- a row added a moment ago votes.  The same
+        checks, ``k <= 64`` (with ``exclude`` the search asks for ``k + 1`` rows); every argument is checked first."""
+        import torch
+        ffi = _ffi()
+        what = "GalleryIndex.classify_live"
+        g = self._gallery
+        g._need_labels(what)
+        inv_t, red = g._vote_args(what, temperature, top, reduce)
+        if not _is_int(k):
+            raise ValueError(f"{what}: k must be an integer, got {k!r}")
+        extra = 0 if exclude is None else 1
+        if k < 1 or k + extra > ffi.KNN_MAX_K:
+            raise ValueError(f"{what}: k = {k}{' (+ 1 for the excluded row)' if extra else ''}, must be in [1, TFIMM_KNN_MAX_K = "
+                             f"{ffi.KNN_MAX_K}{' - 1' if extra else ''}]")
+        parts, tail = self._live_args(int(k) + extra, nprobe, "single", what)
+        t = self._queries(q, what)
+        up_ex = g._exclude(exclude, int(t.shape[0]), what)
+        t = g._upload_rows(t).contiguous()
+        if int(t.shape[0]) == 0:                                # no queries: no search, and the vote launches nothing
+            return g._launch_vote(torch.empty((0, int(k) + extra), dtype=torch.int32, device=t.device),
+                                  torch.empty((0, int(k) + extra), dtype=torch.float32, device=t.device), up_ex, inv_t, red, int(top))
+        indices, scores = self._live(t, int(k) + extra, int(nprobe), parts, "single", tail)
+        return g._launch_vote(indices, scores, up_ex, inv_t, red, int(top))
+
+    def _assignment(self):
+        """the list of every indexed row, int32 (size,), re-derived from ``ids`` and ``offsets``; no synchronisation"""
+        import torch
+        dev = self._ids.device
+        of_pos = torch.repeat_interleave(torch.arange(self.n_lists, dtype=torch.int32, device=dev), self.counts.torch().long(),
+                                         output_size=self.size)
+        out = torch.empty(self.size, dtype=torch.int32, device=dev)
+        out[self._ids.long()] = of_pos
+        return out
+
+    def absorb(self, assignment=None) -> int:
+        """Take the fresh rows into the lists, the centroids unchanged; returns how many.  ``assignment=None`` gives each
+        fresh row its best centroid (tfimm_hip_cluster_assign on that row range alone: work proportional to the fresh rows;
+        the value is ``gallery.assign(index.centroids).clusters[size:]``); or pass the lists yourself, an integer array or
+        ``Tensor`` of shape (fresh,) with values in [0, n_lists) -- host values are checked, a device tensor's are the
+        caller's contract.  Old rows keep their list.  Afterwards the index is exactly what ``gallery.build_index(clusters=
+        Clusters(centroids, old assignment ++ new assignment, ...))`` gives -- rows ascend inside a list, ``stale`` is false,
+        the workspace cache is dropped.  It RE-LAYS THE WHOLE list-ordered copy: one sort of the assignment and one gather of
+        all rows by ``torch`` on the device, and the build's one synchronisation -- one pass over the rows, no k-means.  The
+        centroids do not follow the new rows: after much growth from another distribution recall falls, and a new
+        ``build_index`` is due.  With nothing fresh it returns 0 and does nothing."""
+        import torch
+        what = "GalleryIndex.absorb"
+        fresh = self.fresh
+        new = None
+        if assignment is not None:
+            a = assignment.torch() if isinstance(assignment, Tensor) else assignment
+            if not isinstance(a, torch.Tensor):
+                a = np.asarray(a)
+            kind = str(a.dtype).replace("torch.", "")
+            if not kind.startswith(("int", "uint")):
+                raise ValueError(f"{what}: assignment: expected integers, got {a.dtype}")
+            if tuple(a.shape) != (fresh,):
+                raise ValueError(f"{what}: assignment: expected shape ({fresh},) -- one list per fresh row --, got {tuple(a.shape)}")
+            if fresh and not (isinstance(a, torch.Tensor) and a.is_cuda):
+                lo, hi = int(a.min()), int(a.max())
+                if lo < 0 or hi >= self.n_lists:
+                    raise ValueError(f"{what}: assignment: lists must be in [0, n_lists = {self.n_lists}), got values in [{lo}, {hi}]")
+            new = a
+        if not fresh:
+            return 0
+        dev = self._ids.device
+        if new is None:
+            new = self._assign_fresh()
+        elif not isinstance(new, torch.Tensor):
+            new = torch.from_numpy(np.ascontiguousarray(new).astype(np.int32))
+        self._lay(torch.cat([self._assignment(), new.to(dev).to(torch.int32)]))
+        return fresh
+
+    def _assign_fresh(self):
+        """tfimm_hip_cluster_assign of rows ``size .. len`` against the centroids on the current stream -> int32 (fresh,)"""
+        import torch
+        ffi = _ffi()
+        g, cen, n = self._gallery, self.centroids, self.fresh
+        clusters = torch.empty(n, dtype=torch.int32, device=g._buf.device)
+        scores = torch.empty(n, dtype=torch.float32, device=g._buf.device)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ffi.check(ffi.lib.tfimm_hip_cluster_assign(g._buf.data_ptr() + 2 * self.size * g.pitch, g.pitch, n, cen._buf.data_ptr(), cen.pitch,
+                                                   len(cen), self.dim, clusters.data_ptr(), scores.data_ptr(), st),
+                  "tfimm_hip_cluster_assign")
+        return clusters
 
 
 def _ffi():
